@@ -15,8 +15,13 @@ the same SPMD pipeline.
 value = chunks / end-to-end seconds (whole job; the transcript is fixed, so
 scaling is strong).  ms_per_step = end-to-end wall-clock of one summary.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N
+
+A plain run does only what the headline needs: engine start-up, W warm-up summaries, K timed ones, the JSON
+line.  ``--dump-outputs DIR`` also writes what the last timed step generated (``_dump_outputs``).  ``--full``
+is where everything beyond the headline goes: measurements that take runs of their own (none so far -- the
+per-stage and per-engine figures of the JSON line are by-products of the timed steps and stay in every run).
 
 ``python bench.py --gpus N`` (N > 1) without a torchrun environment launches the N ranks itself (a child
 ``torch.distributed.run``), so both forms measure N ranks; the JSON reports the world size and backend
@@ -77,6 +82,48 @@ def _self_launch(n: int) -> int:
     return subprocess.call(cmd, env=env)
 
 
+def _record_generations(sink: list) -> None:
+    """``--dump-outputs``: append what every ``LLMEngine.generate`` call of this process returns (the list of
+    GenOutput the provider receives) to ``sink``; the timed loop empties it at the start of each step."""
+    from llm_map_reduce_summarizer_amd.engine.engine import LLMEngine
+    inner = LLMEngine.generate
+
+    def generate(self, *a, **kw):
+        outs = inner(self, *a, **kw)
+        sink.append(outs)
+        return outs
+    LLMEngine.generate = generate
+
+
+def _dump_outputs(out_dir: str, rank: int, generations: list, summary: str) -> None:
+    """What the last timed step computed, as float32 ``.npy`` files (a few hundred KB for the headline):
+
+    * ``generate_<k>_tokens.npy`` [requests, longest generation]: the token ids the k-th engine generate of
+      the step returned, one row per request in request order, padded with -1 (one GPU, hierarchical reduce:
+      0 = map, 1 = level-1 reduce, 2 = final reduce);
+    * ``generate_<k>_prompt_lens.npy`` [requests]: the prompt length of each of those requests;
+    * ``summary_utf8.npy``: the bytes of the final summary, UTF-8.
+
+    Token ids and byte values are exact in float32.  The transcript, the weights and the sampling seeds are
+    functions of the arguments alone, so two builds run with the same arguments can be compared file by file.
+    Rank 0 writes these names; a rank r > 0 of a multi-process job writes its own engines' generations as
+    ``rank<r>_generate_...`` (data-parallel ranks hold different requests)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    pre = "" if rank == 0 else "rank%d_" % rank
+    for k, outs in enumerate(generations):
+        width = max([len(o.token_ids) for o in outs] + [1])
+        toks = np.full((len(outs), width), -1.0, dtype=np.float32)
+        for i, o in enumerate(outs):
+            toks[i, :len(o.token_ids)] = o.token_ids
+        np.save(os.path.join(out_dir, "%sgenerate_%02d_tokens.npy" % (pre, k)), toks)
+        np.save(os.path.join(out_dir, "%sgenerate_%02d_prompt_lens.npy" % (pre, k)),
+                np.asarray([o.prompt_len for o in outs], dtype=np.float32))
+    if rank == 0:
+        np.save(os.path.join(out_dir, "summary_utf8.npy"),
+                np.frombuffer(summary.encode("utf-8"), dtype=np.uint8).astype(np.float32))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -108,6 +155,12 @@ def main() -> int:
                          "reserved); a small value forces a multi-level reduce with short pinned summaries "
                          "(labelled variant, never the headline)")
     ap.add_argument("--profile", default=None, metavar="DIR", help="torch.profiler trace of the timed steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one generated as DIR/<name>.npy (float32: the "
+                         "token ids of every engine generate and the final summary's bytes)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what goes beyond the headline figure (nothing so far: every other figure of the "
+                         "JSON line is a by-product of the timed steps)")
     ap.add_argument("--log-level", default="WARNING")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -150,7 +203,12 @@ def main() -> int:
     n_chunks_est = max(64, int(args.hours * 8))
     provider.warm(capture_batch=n_chunks_est if not args.no_graphs else None)
 
+    generations: list = []
+    if args.dump_outputs:
+        _record_generations(generations)
+
     def one():
+        del generations[:]
         return asyncio.run(summarizer.summarize(transcript))
 
     for i in range(args.warmup):
@@ -257,6 +315,8 @@ def main() -> int:
         "ar_recoveries": ar_recoveries,
         "engine_rank0": {k: (round(v, 3) if isinstance(v, float) else v) for k, v in eng.items()},
     }
+    if args.dump_outputs and reports:
+        _dump_outputs(args.dump_outputs, rank, generations, rep.get("summary", ""))
     if rank == 0:
         print(json.dumps(out), flush=True)
     rc = 0

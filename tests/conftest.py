@@ -7,7 +7,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-REFERENCE_EXAMPLE = "/root/reference/transcript-example.json"
+REFERENCE_EXAMPLE = os.path.join(ROOT, "tests", "golden", "transcript-example.json.xz")
 
 
 def pytest_configure(config):
@@ -17,12 +17,11 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def example_transcript():
-    """The reference's bundled example (read-only mount); synthetic stand-in elsewhere."""
+    """The reference's bundled example transcript (a compressed copy under tests/golden/)."""
     import json
-    if os.path.isfile(REFERENCE_EXAMPLE):
-        with open(REFERENCE_EXAMPLE, encoding="utf-8") as f:
-            return json.load(f)
-    pytest.skip("reference example transcript not available on this machine")
+    import lzma
+    with lzma.open(REFERENCE_EXAMPLE, "rt", encoding="utf-8") as f:
+        return json.load(f)
 
 
 @pytest.fixture(scope="session")

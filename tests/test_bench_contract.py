@@ -3,6 +3,7 @@ bench.py --gpus N --steps K --warmup W`` prints exactly ONE JSON line (rank 0) w
 the step accounting and the config -- for a single process and for 2 ranks (data-parallel and
 tensor-parallel stages), on a tiny model so it runs in seconds.  The 8-GPU node runs the same code
 path with RCCL."""
+import hashlib
 import json
 import os
 import socket
@@ -69,6 +70,36 @@ def test_bench_prints_one_json_line(world, extra):
         assert r["calls_per_step"] >= 1 and r["measured_s"] > 0
         assert r["predicted_s"] is not None and r["predicted_s"] > 0
         assert r["tp"] == (2 if extra == ("--parallel", "tp") else 1)
+
+
+def test_bench_dumps_outputs_and_full(tmp_path):
+    """``--dump-outputs DIR`` writes what the last timed step generated as float32 ``.npy`` files, identical from
+    run to run with the same arguments; ``--full`` (everything beyond the headline) exits 0 with the same line and
+    the same outputs; ``--steps`` sets the number of timed steps."""
+    import numpy as np
+    a, b = tmp_path / "a", tmp_path / "b"
+    plain = _run(1, "--dump-outputs", str(a))
+    full = _run(1, "--dump-outputs", str(b), "--full", "--steps", "1")
+    assert plain["steps"] == 2 and full["steps"] == 1
+    assert plain["timed_work"]["requests"] == 2 * full["timed_work"]["requests"] > 0
+    assert KEYS <= set(full) and full["metric"] == plain["metric"] and full["ms_per_step"] > 0
+    names = sorted(p.name for p in a.iterdir())
+    assert names == sorted(p.name for p in b.iterdir())
+    assert "summary_utf8.npy" in names and "generate_00_tokens.npy" in names
+    # one engine generate per stage of the step: every request's pinned 6 tokens, in request order
+    n_gen = sum(n.endswith("_tokens.npy") for n in names)
+    assert n_gen == len(plain["stages"]) and all(n.endswith(".npy") for n in names)
+    rows = 0
+    for n in names:
+        x, y = np.load(a / n), np.load(b / n)
+        assert x.dtype == np.float32 and x.shape == y.shape and np.array_equal(x, y), n
+        if n.endswith("_tokens.npy"):
+            assert x.shape[1] == 6 and (x >= 0).all() and (x == np.floor(x)).all()
+            rows += x.shape[0]
+    assert rows == full["timed_work"]["requests"]
+    assert bytes(np.load(a / "summary_utf8.npy").astype(np.uint8)).decode("utf-8").strip()
+    assert hashlib.sha256(bytes(np.load(a / "summary_utf8.npy").astype(np.uint8))).hexdigest()[:16] \
+        == plain["summary_sha16"]
 
 
 def test_bench_self_launches_ranks():

@@ -1,11 +1,6 @@
-import importlib.util
-import os
-import sys
-import types
-
 import pytest
 
-from llm_map_reduce_summarizer_amd.engine.tokenizer import get_tokenizer
+import _golden as G
 from llm_map_reduce_summarizer_amd.pipeline.chunker import Chunker, split_sentences
 from llm_map_reduce_summarizer_amd.pipeline.preprocess import preprocess_transcript
 
@@ -75,47 +70,17 @@ def test_overlap_block():
     assert "PREVIOUS CONTEXT" in chunks[1]["text_with_context"]
 
 
-def _reference_chunker_module():
-    path = "/root/reference/big_chunkeroosky.py"
-    if not os.path.isfile(path):
-        pytest.skip("reference sources not mounted")
-    tok = get_tokenizer()
-
-    class Enc:
-        def encode(self, text):
-            return tok.encode_ordinary(text)
-
-    fake_tiktoken = types.SimpleNamespace(get_encoding=lambda name: Enc())
-
-    class Punkt:
-        def tokenize(self, text):
-            return split_sentences(text)
-
-    fake_nltk = types.ModuleType("nltk")
-    fake_nltk.data = types.SimpleNamespace(find=lambda *_: True)
-    fake_nltk.tokenize = types.SimpleNamespace(PunktSentenceTokenizer=Punkt)
-    saved = {k: sys.modules.get(k) for k in ("nltk", "tiktoken")}
-    sys.modules["nltk"], sys.modules["tiktoken"] = fake_nltk, fake_tiktoken
-    try:
-        spec = importlib.util.spec_from_file_location("ref_chunker", path)
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
-    return mod
+@pytest.fixture(scope="module")
+def reference_chunks():
+    """What the reference's chunker returned per budget, with this project's tokenizer and sentence splitter
+    injected in place of tiktoken / nltk (tools/record_reference_golden.py)."""
+    return G.load_results()["chunks"]
 
 
-@pytest.mark.parametrize("budget", [600, 2000, 4000])
-def test_differential_vs_reference(example_transcript, budget, capsys):
-    """Same tokenizer + sentence splitter injected into the reference: identical chunks."""
-    ref = _reference_chunker_module()
-    segs = preprocess_transcript(example_transcript["segments"][:2500], max_segment_duration=600)
+@pytest.mark.parametrize("budget", G.CHUNKER_BUDGETS)
+def test_differential_vs_reference(example_transcript, reference_chunks, budget, capsys):
+    """Same tokenizer + sentence splitter injected into the reference: identical chunks (its recorded results)."""
+    segs = preprocess_transcript(example_transcript["segments"][:G.CHUNKER_EXAMPLE_SEGMENTS], **G.CHUNKER_PREPROCESS)
     a = Chunker(budget, position_mode="reference", reference_quirks=True)
     mine = a.postprocess_chunks(a.chunk_transcript(segs))
-    r = ref.BigChunkeroosky(max_tokens_per_chunk=budget)
-    theirs = r.postprocess_chunks(r.chunk_transcript(segs))
-    assert mine == theirs
+    G.assert_same(mine, reference_chunks[str(budget)])

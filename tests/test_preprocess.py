@@ -1,9 +1,7 @@
 """Golden numbers from SURVEY.md §4 (exact: preprocessing never tokenizes)."""
-import importlib.util
-import os
-
 import pytest
 
+import _golden as G
 from llm_map_reduce_summarizer_amd.pipeline import preprocess as P
 
 
@@ -58,29 +56,21 @@ def test_single_segment_group_returned_as_is():
     assert "is_combined" not in out[0] and out[0]["text"] == "long"
 
 
-def _load_reference_module():
-    path = "/root/reference/preprocessor.py"
-    if not os.path.isfile(path):
-        pytest.skip("reference sources not mounted")
-    spec = importlib.util.spec_from_file_location("ref_preprocessor", path)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+@pytest.fixture(scope="module")
+def reference_results():
+    """What the reference's preprocessor returned for the cases below (tools/record_reference_golden.py)."""
+    return G.load_results()
 
 
-@pytest.mark.parametrize("kwargs", [{}, {"time_interval_seconds": 60}, {"time_interval_seconds": 300},
-                                    {"merge_same_speaker": False, "time_interval_seconds": 120},
-                                    {"max_segment_duration": 45, "preserve_timestamps": False}])
-def test_differential_vs_reference(example_transcript, kwargs, capsys):
-    """Bit-identical output to the reference implementation (pure stdlib module)."""
-    ref = _load_reference_module()
-    segs = example_transcript["segments"][:1500]
-    assert P.preprocess_transcript(segs, **kwargs) == ref.preprocess_transcript(segs, **kwargs)
+@pytest.mark.parametrize("kwargs", G.PREPROCESS_CASES)
+def test_differential_vs_reference(example_transcript, reference_results, kwargs, capsys):
+    """Bit-identical output to the reference implementation (its recorded results)."""
+    segs = example_transcript["segments"][:G.PREPROCESS_EXAMPLE_SEGMENTS]
+    G.assert_same(P.preprocess_transcript(segs, **kwargs), reference_results["preprocess_example"][G.key(kwargs)])
 
 
-def test_multispeaker_synthetic_differential():
+def test_multispeaker_synthetic_differential(reference_results):
     from llm_map_reduce_summarizer_amd.utils.synth import synthetic_transcript
-    ref = _load_reference_module()
-    segs = synthetic_transcript(1.0, seed=3, n_speakers=3)["segments"]
-    for kw in ({}, {"time_interval_seconds": 90}):
-        assert P.preprocess_transcript(segs, **kw) == ref.preprocess_transcript(segs, **kw)
+    segs = synthetic_transcript(**G.PREPROCESS_SYNTH)["segments"]
+    for kw in G.PREPROCESS_SYNTH_CASES:
+        G.assert_same(P.preprocess_transcript(segs, **kw), reference_results["preprocess_synthetic"][G.key(kw)])
