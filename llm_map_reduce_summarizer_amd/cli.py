@@ -64,6 +64,10 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--position-mode", choices=["transcript", "reference"], default="transcript")
     g.add_argument("--max-new-tokens", type=int, default=None, help="override $MAX_TOKENS")
     g.add_argument("--temperature", type=float, default=None, help="override $TEMPERATURE (map)")
+    g.add_argument("--top-p", type=float, default=None,
+                   help="override $TOP_P: nucleus sampling, map and reduce (0 < p <= 1; 1.0 = off)")
+    g.add_argument("--top-k", type=int, default=None,
+                   help="override $TOP_K: sample among the k most likely tokens, map and reduce (0 = off)")
     g.add_argument("--fault-inject", type=float, default=0.0, help="mock provider: failure probability")
     g.add_argument("--profile", default=None, metavar="DIR",
                    help="torch.profiler trace of the run: DIR/trace_rank{r}.json + top-kernel table")
@@ -120,8 +124,24 @@ def setup_logging(level: str) -> None:
     root.setLevel(getattr(logging, str(level).upper(), logging.INFO))
 
 
-async def async_main(args: argparse.Namespace) -> int:
+def config_from_args(args: argparse.Namespace):
+    """The run's LLMConfig: the environment's values with the generation flags on top."""
     from .config import LLMConfig
+    cfg = LLMConfig()
+    if args.max_new_tokens is not None:
+        cfg.MAX_TOKENS = args.max_new_tokens
+    if args.temperature is not None:
+        cfg.TEMPERATURE = args.temperature
+    if args.top_p is not None:
+        cfg.TOP_P = args.top_p
+    if args.top_k is not None:
+        cfg.TOP_K = args.top_k
+    if cfg.TOP_K < 0 or not 0.0 < cfg.TOP_P <= 1.0:
+        raise SystemExit("top-k must be >= 0 and top-p in (0, 1], got %r / %r" % (cfg.TOP_K, cfg.TOP_P))
+    return cfg
+
+
+async def async_main(args: argparse.Namespace) -> int:
     from .pipeline.executor import LLMExecutor
     from .pipeline.orchestrator import TranscriptSummarizer, _is_writer
 
@@ -132,11 +152,7 @@ async def async_main(args: argparse.Namespace) -> int:
         log.error("failed to load transcript %s: %s", args.input, e)
         return 1
 
-    cfg = LLMConfig()
-    if args.max_new_tokens is not None:
-        cfg.MAX_TOKENS = args.max_new_tokens
-    if args.temperature is not None:
-        cfg.TEMPERATURE = args.temperature
+    cfg = config_from_args(args)
     provider = args.provider or cfg.DEFAULT_PROVIDER
     popts = {}
     if provider == "mock":

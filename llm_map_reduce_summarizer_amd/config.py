@@ -63,6 +63,8 @@ class LLMConfig:
         "ENGINE_MAX_NUM_SEQS": ("256", int), "ENGINE_KV_FRACTION": ("0.6", float),
         "ENGINE_KV_DTYPE": ("bf16", str),
         "REDUCE_TEMPERATURE": ("0.2", float),
+        # sampling filters of the map and the reduce stage (1.0 / 0 = off)
+        "TOP_P": ("1.0", float), "TOP_K": ("0", int),
         # hosted-provider endpoints (new): point the adapters at any compatible server
         "OPENAI_BASE_URL": ("https://api.openai.com/v1", str),
         "ANTHROPIC_BASE_URL": ("https://api.anthropic.com/v1", str),

@@ -18,6 +18,17 @@
 //          holds when it is replayed (generate(ignore_eos=True) writes -1s),
 //          not the one it held when the graph was captured.  A retired row keeps its position, so a captured decode
 //          graph can keep running it harmlessly until the host drops it.
+// filter:  top-k / top-p (ops/reference.py nucleus_threshold is the definition).  bf16 logits have at
+//          most 65536 distinct values, so a per-row integer histogram over the 16-bit order-preserving
+//          key gives the cut exactly, without a sort or a softmax pass:
+//          filter_hist   grid (FILTER_R, B): workgroup (r, b) counts the keys [r, r + 1) * 65536 / R of
+//                        row b in LDS (u32, LDS atomics) and stores its slice of hist[b] with plain 16-B
+//                        stores, with the total of every 64-bin chunk -- no global atomics;
+//          filter_select one workgroup per row walks the bins from the top: integer counts for top-k,
+//                        fp32 mass n * exp((v - v1) / tau) for top-p (a fixed order: 64 bins per thread,
+//                        then a block scan -- no float atomics), and writes thresh[b] (-inf: no filter);
+//          sample_kernel<true> then skips every token with logit < thresh[b].  Rows without a filter
+//          (or greedy, or done) cost one early-exit workgroup each and sample exactly as unfiltered.
 // Tensor parallel (vocab-parallel LM head): each rank scans its vocab shard with
 // tok_offset = rank * V_local -- the noise is a function of the GLOBAL token id, so the
 // per-rank winners max-reduced across ranks (8 bytes per row, parallel/custom_ar.py) give the
@@ -38,14 +49,225 @@ __device__ __forceinline__ unsigned int order_key(float v) {
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
+// ------------------------------------------------------------------ top-k / top-p filter
+constexpr int FILTER_BINS = 65536;                 // one per bf16 bit pattern
+constexpr int FILTER_R = 4;                        // histogram workgroups per row
+constexpr int FILTER_SLICE = FILTER_BINS / FILTER_R;  // 16384 u32 bins = 64 KiB of LDS
+constexpr int HIST_THREADS = 1024;
+constexpr int SELECT_THREADS = 1024;
+constexpr int SELECT_CHUNK = FILTER_BINS / SELECT_THREADS;  // 64 bins per thread
+// a row of the workspace: the 65536 bins, then the total count of every 64-bin chunk (the select kernel
+// reads the bins of non-empty chunks only: a row of logits populates a few percent of them)
+constexpr int FILTER_CHUNKS = FILTER_BINS / SELECT_CHUNK;
+constexpr int FILTER_ROW = FILTER_BINS + FILTER_CHUNKS;
+
+// order_key on the 16 bits of a bf16, -0 canonicalised to +0; NaNs -> -1 (no bin)
+__device__ __forceinline__ int key16(unsigned int h) {
+    if ((h & 0x7fffu) > 0x7f80u) return -1;
+    if (h == 0x8000u) h = 0u;
+    return (int)((h & 0x8000u) ? (~h & 0xffffu) : (h | 0x8000u));
+}
+
+__device__ __forceinline__ float key16_value(int key) {
+    const unsigned int h = key >= 0x8000 ? ((unsigned int)key & 0x7fffu) : (~(unsigned int)key & 0xffffu);
+    return bf16_bits_to_f32(h);
+}
+
+// exp((v - v1) / tau) of the level with this key; exactly 1 for the top level (also when v1 is infinite)
+__device__ __forceinline__ float level_weight(int key, int top_key, float v1, float inv_tau) {
+    return key == top_key ? 1.f : __expf((key16_value(key) - v1) * inv_tau);
+}
+
+__device__ __forceinline__ bool filter_active(float tau, int k, float p) { return tau > 0.f && (k > 0 || p < 1.f); }
+
+__global__ __launch_bounds__(HIST_THREADS) void filter_hist_kernel(const bf16* __restrict__ logits, int ld, int V,
+                                                                   const float* __restrict__ temps,
+                                                                   const int* __restrict__ top_k,
+                                                                   const float* __restrict__ top_p,
+                                                                   const int* __restrict__ done,
+                                                                   unsigned int* __restrict__ hist) {
+    __shared__ unsigned int bins[FILTER_SLICE];
+    const int b = blockIdx.y;
+    if (!filter_active(temps[b], top_k[b], top_p[b]) || done[b]) return;  // block-uniform
+    const int k0 = blockIdx.x * FILTER_SLICE;
+    uint4* bins4 = reinterpret_cast<uint4*>(bins);
+    for (int i = threadIdx.x; i < FILTER_SLICE / 4; i += HIST_THREADS) bins4[i] = make_uint4(0u, 0u, 0u, 0u);
+    __syncthreads();
+    const bf16* row = logits + (size_t)b * ld;
+    const unsigned short* rbits = reinterpret_cast<const unsigned short*>(row);
+    for (int c = threadIdx.x * 8; c < V; c += HIST_THREADS * 8) {
+        unsigned int h[8];
+        if (c + 8 <= V) {
+            const uint4 v = *reinterpret_cast<const uint4*>(row + c);
+            h[0] = v.x & 0xffffu; h[1] = v.x >> 16; h[2] = v.y & 0xffffu; h[3] = v.y >> 16;
+            h[4] = v.z & 0xffffu; h[5] = v.z >> 16; h[6] = v.w & 0xffffu; h[7] = v.w >> 16;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) h[j] = c + j < V ? (unsigned int)rbits[c + j] : 0x7fffu;  // NaN: no bin
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const unsigned int rel = (unsigned int)(key16(h[j]) - k0);  // key -1 (NaN) wraps out of range
+            if (rel < (unsigned int)FILTER_SLICE) atomicAdd(&bins[rel], 1u);
+        }
+    }
+    __syncthreads();
+    unsigned int* hrow = hist + (size_t)b * FILTER_ROW;
+    uint4* out4 = reinterpret_cast<uint4*>(hrow + k0);
+    for (int i = threadIdx.x; i < FILTER_SLICE / 4; i += HIST_THREADS) out4[i] = bins4[i];
+    if (threadIdx.x < FILTER_SLICE / SELECT_CHUNK) {  // this slice's chunk totals (lane-rotated: no bank conflict)
+        unsigned int t = 0;
+#pragma unroll 8
+        for (int i = 0; i < SELECT_CHUNK; ++i)
+            t += bins[threadIdx.x * SELECT_CHUNK + ((i + threadIdx.x) & (SELECT_CHUNK - 1))];
+        hrow[FILTER_BINS + k0 / SELECT_CHUNK + threadIdx.x] = t;
+    }
+}
+
+// Exclusive prefix of (count, mass) over the block's threads in thread order (thread 0 = the top chunk):
+// wave inclusive scan, then the earlier waves' totals added one after the other -- a fixed order.
+__device__ __forceinline__ void select_scan(int cnt, float mass, int* s_cnt, float* s_mass, int& ex_cnt,
+                                            float& ex_mass, int& tot_cnt) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    int ic = cnt;
+    float im = mass;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int oc = __shfl_up(ic, o, 64);
+        const float om = __shfl_up(im, o, 64);
+        if (lane >= o) { ic += oc; im = om + im; }
+    }
+    if (lane == 63) { s_cnt[wid] = ic; s_mass[wid] = im; }
+    __syncthreads();
+    int pc = 0, tc = 0;
+    float pm = 0.f;
+    for (int w = 0; w < SELECT_THREADS / 64; ++w) {
+        if (w < wid) { pc += s_cnt[w]; pm += s_mass[w]; }
+        tc += s_cnt[w];
+    }
+    const float prev = __shfl_up(im, 1, 64);
+    ex_cnt = pc + ic - cnt;
+    ex_mass = lane == 0 ? pm : pm + prev;
+    tot_cnt = tc;
+    __syncthreads();
+}
+
+__device__ __forceinline__ int block_max_int(int v, int* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int m = red[0];
+    for (int w = 1; w < SELECT_THREADS / 64; ++w) m = max(m, red[w]);
+    __syncthreads();
+    return m;
+}
+
+__global__ __launch_bounds__(SELECT_THREADS) void filter_select_kernel(const unsigned int* __restrict__ hist, int V,
+                                                                       const float* __restrict__ temps,
+                                                                       const int* __restrict__ top_k,
+                                                                       const float* __restrict__ top_p,
+                                                                       const int* __restrict__ done,
+                                                                       float* __restrict__ thresh) {
+    __shared__ int s_cnt[SELECT_THREADS / 64];
+    __shared__ float s_mass[SELECT_THREADS / 64];
+    __shared__ int s_red[SELECT_THREADS / 64];
+    __shared__ int s_jk;
+    __shared__ float s_z;
+    const int b = blockIdx.x;
+    const float tau = temps[b];
+    const int k = top_k[b];
+    const float p = top_p[b];
+    if (!filter_active(tau, k, p) || done[b]) {  // block-uniform
+        if (threadIdx.x == 0) thresh[b] = -INFINITY;
+        return;
+    }
+    // thread t owns the keys hi, hi - 1, ..., hi - 63 (descending: thread 0 holds the largest values);
+    // n[i] = count of key lo + i
+    const int lo = FILTER_BINS - SELECT_CHUNK * ((int)threadIdx.x + 1);
+    unsigned int n[SELECT_CHUNK];
+    const unsigned int* hrow = hist + (size_t)b * FILTER_ROW;
+    const uint4* src = reinterpret_cast<const uint4*>(hrow + lo);
+    const bool any = hrow[FILTER_BINS + lo / SELECT_CHUNK] != 0u;  // coalesced; most chunks are empty
+#pragma unroll
+    for (int i = 0; i < SELECT_CHUNK / 4; ++i) {
+        const uint4 v = any ? src[i] : make_uint4(0u, 0u, 0u, 0u);
+        n[4 * i] = v.x; n[4 * i + 1] = v.y; n[4 * i + 2] = v.z; n[4 * i + 3] = v.w;
+    }
+    int cnt = 0, top = -1;
+#pragma unroll
+    for (int i = 0; i < SELECT_CHUNK; ++i) {
+        cnt += (int)n[i];
+        if (n[i]) top = lo + i;
+    }
+    const int top_key = block_max_int(top, s_red);
+    if (top_key < 0) {  // nothing but NaNs
+        if (threadIdx.x == 0) thresh[b] = -INFINITY;
+        return;
+    }
+    const float v1 = key16_value(top_key);
+    const float inv_tau = 1.f / tau;
+    // level weights n * exp((v - v1) / tau), summed downwards within the chunk
+    float mass = 0.f;
+#pragma unroll
+    for (int i = SELECT_CHUNK - 1; i >= 0; --i) {
+        const int key = lo + i;
+        if (n[i]) mass += (float)n[i] * level_weight(key, top_key, v1, inv_tau);
+    }
+    int ex_cnt, tot;
+    float ex_mass;
+    select_scan(cnt, mass, s_cnt, s_mass, ex_cnt, ex_mass, tot);
+    // top-k: the first level whose cumulative count reaches k (all levels for k = 0 or k >= V)
+    const int k_eff = (k <= 0 || k >= V) ? tot : min(k, tot);
+    if (ex_cnt < k_eff && k_eff <= ex_cnt + cnt) {  // exactly one thread
+        int c = ex_cnt, jk = -1;
+        float m = ex_mass, z = 0.f;
+#pragma unroll
+        for (int i = SELECT_CHUNK - 1; i >= 0; --i) {
+            const int key = lo + i;
+            if (n[i] && jk < 0) {
+                c += (int)n[i];
+                m += (float)n[i] * level_weight(key, top_key, v1, inv_tau);
+                if (c >= k_eff) { jk = key; z = m; }
+            }
+        }
+        s_jk = jk;
+        s_z = z;
+    }
+    __syncthreads();
+    const int jk = s_jk;
+    int cut = jk;
+    if (p < 1.f) {
+        // top-p over the top-k set: the first level whose cumulative mass reaches p * Z
+        const float target = p * s_z;
+        int cand = -1;
+        float m = ex_mass;
+#pragma unroll
+        for (int i = SELECT_CHUNK - 1; i >= 0; --i) {
+            const int key = lo + i;
+            if (n[i] && key >= jk && cand < 0) {
+                m += (float)n[i] * level_weight(key, top_key, v1, inv_tau);
+                if (m >= target) cand = key;
+            }
+        }
+        cand = block_max_int(cand, s_red);
+        if (cand >= 0) cut = cand;
+    }
+    if (threadIdx.x == 0) thresh[b] = key16_value(cut);
+}
+
+template <bool FILTER>
 __global__ __launch_bounds__(256) void sample_kernel(const bf16* __restrict__ logits, int ld, int V, int tok_offset,
                                                      const float* __restrict__ temps,
                                                      const long long* __restrict__ seeds,
                                                      const int* __restrict__ positions,
-                                                     unsigned long long* __restrict__ result, int seg_len) {
+                                                     unsigned long long* __restrict__ result, int seg_len,
+                                                     const float* __restrict__ thresh) {
     __shared__ unsigned long long red[4];
     const int b = blockIdx.y;
     const float tau = temps[b];
+    float th = -INFINITY;
+    if constexpr (FILTER) th = thresh[b];
     const float inv_tau = tau > 0.f ? 1.f / tau : 0.f;
     const unsigned long long key0 =
         mix64((unsigned long long)seeds[b] * 0x9E3779B97F4A7C15ULL + (unsigned long long)(positions[b] + 1));
@@ -65,6 +287,9 @@ __global__ __launch_bounds__(256) void sample_kernel(const bf16* __restrict__ lo
         for (int j = 0; j < 8; ++j) {
             const int tok = tok_offset + c + j;
             float v = f[j];
+            if constexpr (FILTER) {
+                if (v < th) continue;  // outside the kept set: no hash, no key
+            }
             if (tau > 0.f) {
                 const unsigned long long h = mix64(key0 ^ ((unsigned long long)tok * 0xD1B54A32D192ED03ULL));
                 const float u = ((float)(h >> 40) + 0.5f) * (1.f / 16777216.f);
@@ -115,8 +340,8 @@ static int launch_keys(const void* logits, int ld, int B, int V, int tok_offset,
     const int nseg = 32;
     int seg_len = ceil_div(V, nseg);
     seg_len = (seg_len + 7) & ~7;
-    sample_kernel<<<dim3(nseg, B), 256, 0, s>>>((const bf16*)logits, ld, V, tok_offset, temps, seeds, positions,
-                                                (unsigned long long*)result, seg_len);
+    sample_kernel<false><<<dim3(nseg, B), 256, 0, s>>>((const bf16*)logits, ld, V, tok_offset, temps, seeds,
+                                                       positions, (unsigned long long*)result, seg_len, nullptr);
     return (int)hipGetLastError();
 }
 
@@ -143,6 +368,43 @@ MRSUM_API int mrsum_sample(const void* logits, int ld, int B, int V, const float
                            hipStream_t s) {
     if (B <= 0) return 0;
     int e = launch_keys(logits, ld, B, V, 0, temps, seeds, positions, result, s);
+    if (e) return e;
+    sample_finish_kernel<<<ceil_div(B, 64), 64, 0, s>>>((unsigned long long*)result, next_ids, positions_rw,
+                                                        gen_count, max_new, out_tokens, out_stride, done, eos, B);
+    return (int)hipGetLastError();
+}
+
+// thresh[b] = the top-k / top-p threshold of row b (-inf: no filter, greedy or done).  hist: workspace of
+// B x (65536 + 1024) u32 (ops.hip.FilterWorkspace), fully rewritten for every filtered row: no state is
+// carried between launches.
+MRSUM_API int mrsum_sample_thresh(const void* logits, int ld, int B, int V, const float* temps, const int* top_k,
+                                  const float* top_p, const int* done, float* thresh, void* hist, hipStream_t s) {
+    if (B <= 0) return 0;
+    filter_hist_kernel<<<dim3(FILTER_R, B), HIST_THREADS, 0, s>>>((const bf16*)logits, ld, V, temps, top_k, top_p,
+                                                                  done, (unsigned int*)hist);
+    int e = (int)hipGetLastError();
+    if (e) return e;
+    filter_select_kernel<<<B, SELECT_THREADS, 0, s>>>((const unsigned int*)hist, V, temps, top_k, top_p, done,
+                                                      thresh);
+    return (int)hipGetLastError();
+}
+
+// mrsum_sample with a top-k / top-p filter per row: thresholds, Gumbel-max over the kept tokens, finish --
+// all on stream s, capturable.
+MRSUM_API int mrsum_sample_filtered(const void* logits, int ld, int B, int V, const float* temps,
+                                    const long long* seeds, const int* positions, const int* top_k,
+                                    const float* top_p, float* thresh, void* hist, void* result, int* next_ids,
+                                    int* positions_rw, int* gen_count, const int* max_new, int* out_tokens,
+                                    int out_stride, int* done, const int* eos, hipStream_t s) {
+    if (B <= 0) return 0;
+    int e = mrsum_sample_thresh(logits, ld, B, V, temps, top_k, top_p, done, thresh, hist, s);
+    if (e) return e;
+    const int nseg = 32;
+    int seg_len = ceil_div(V, nseg);
+    seg_len = (seg_len + 7) & ~7;
+    sample_kernel<true><<<dim3(nseg, B), 256, 0, s>>>((const bf16*)logits, ld, V, 0, temps, seeds, positions,
+                                                      (unsigned long long*)result, seg_len, thresh);
+    e = (int)hipGetLastError();
     if (e) return e;
     sample_finish_kernel<<<ceil_div(B, 64), 64, 0, s>>>((unsigned long long*)result, next_ids, positions_rw,
                                                         gen_count, max_new, out_tokens, out_stride, done, eos, B);

@@ -24,7 +24,7 @@ from __future__ import annotations
 import logging
 import os
 import time
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -40,10 +40,16 @@ log = logging.getLogger("mrsum.engine")
 
 BUCKETS = (1, 2, 4, 8, 16, 24, 32, 40, 48, 64, 80, 96, 128, 160, 192, 224, 256)
 MAX_WINDOW = 256  # decode steps between host syncs when no row can stop early (LLMEngine._window)
+_I32_MAX = 2 ** 31 - 1  # DecodeState.top_k is int32; any k >= the vocabulary size means "off"
 
 
 def _always() -> bool:
     return True
+
+
+def _any_filtered(seqs) -> bool:
+    """Whether any of these sequences samples through a top-k / top-p filter (host-side: _Seq.params)."""
+    return any(s.params.filtered for s in seqs)
 
 
 @dataclass
@@ -51,6 +57,20 @@ class SamplingParams:
     max_new_tokens: int = 1000
     temperature: float = 0.3
     seed: int = 0
+    top_k: int = 0  # keep the k most likely tokens (ties at the cut all stay); 0 = off
+    top_p: float = 1.0  # nucleus: the smallest top set holding this share of the top-k mass; 1.0 = off
+
+    @property
+    def filtered(self) -> bool:
+        """Whether sampling with these parameters is restricted at all (greedy rows never are)."""
+        return self.temperature > 0 and (self.top_k > 0 or self.top_p < 1.0)
+
+    def validate(self) -> None:
+        k, p = self.top_k, self.top_p
+        if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+            raise ValueError("top_k must be an integer >= 0, got %r" % (k,))
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 < p <= 1.0:
+            raise ValueError("top_p must be a number in (0, 1], got %r" % (p,))
 
 
 @dataclass
@@ -98,6 +118,15 @@ class DecodeState:
         self.result = torch.zeros(max_seqs, dtype=torch.int64, device=device)
         self.temps = torch.zeros(max_seqs, dtype=torch.float32, device=device)
         self.seeds = torch.zeros(max_seqs, dtype=torch.int64, device=device)
+        # top-k / top-p filter of every row (0 / 1.0 = off) and the logit threshold the sampler derives
+        # from them at every filtered step (ops.reference.nucleus_threshold)
+        self.top_k = torch.zeros(max_seqs, **i32)
+        self.top_p = torch.ones(max_seqs, dtype=torch.float32, device=device)
+        self.thresh = torch.full((max_seqs,), float("-inf"), dtype=torch.float32, device=device)
+        self.filter_ws = None
+        if self.temps.is_cuda:
+            from ..ops.hip import FilterWorkspace
+            self.filter_ws = FilterWorkspace(max_seqs, self.temps.device)  # allocated on first filtered use
         # the sampler's finish kernel reads these 4 stop ids from device memory at every launch (-1 =
         # unused slot), so captured decode graphs follow the stop set at REPLAY time (set_eos)
         self.eos = torch.full((4,), -1, **i32)
@@ -113,7 +142,7 @@ class DecodeState:
         self.eos_ids = ids
 
     _ROW_FIELDS = ("next_ids", "positions", "block_tables", "gen_count", "max_new", "out_tokens", "done", "result",
-                   "temps", "seeds")
+                   "temps", "seeds", "top_k", "top_p", "thresh")
 
     def view(self, start: int, n: int) -> "DecodeState":
         v = object.__new__(DecodeState)
@@ -122,6 +151,8 @@ class DecodeState:
             setattr(v, f, getattr(self, f)[start:start + n])
         v.seq_idx = self.seq_idx[:n]
         v.eos, v.eos_ids = self.eos, self.eos_ids
+        v.filter_ws = self.filter_ws
+        v.filtered = False  # set by the engine on the view of a batch with a top-k / top-p row
         return v
 
     def move_row(self, src: int, dst: int) -> None:
@@ -272,13 +303,15 @@ class LLMEngine:
             log.warning("TP=%d without the custom all-reduce: decode hipGraphs disabled", self.model.tp_size)
             self.use_graphs = False
         # decode graphs / attention workspaces per (batch bucket, context class): the attention's split
-        # plan depends on how long the contexts get (ops.hip.decode_attn_plan)
-        self._graphs: Dict[Tuple[int, int], "torch.cuda.CUDAGraph"] = {}
+        # plan depends on how long the contexts get (ops.hip.decode_attn_plan); a graph whose sampler runs
+        # the top-k / top-p filter has its own key (_graph_key)
+        self._graphs: Dict[tuple, "torch.cuda.CUDAGraph"] = {}
         self._ctx_cls = 0
         self._on_prefill = None
         self._workspaces: Dict[Tuple[int, int], object] = {}
         self.stats = {"prefill_tokens": 0, "prefill_s": 0.0, "decode_steps": 0, "decode_tokens": 0,
-                      "decode_s": 0.0, "generate_calls": 0, "graph_captures": 0, "peak_active": 0}
+                      "decode_s": 0.0, "generate_calls": 0, "graph_captures": 0, "peak_active": 0,
+                      "filtered_steps": 0}
 
     # ------------------------------------------------------------------ helpers
     def _bucket(self, n: int) -> int:
@@ -326,7 +359,7 @@ class LLMEngine:
             # tensor parallel, one pass: the layer-major path (sequence-parallel norms, async reductions)
             x = self._pass_inputs(seqs, [(0, len(s.prompt)) for s in seqs], paged=True)
             logits = self.model.prefill_passes([x], self.state.block_tables, self.kv.k, self.kv.v,
-                                               gather=not self.model.tp_sampling)
+                                               gather=self._gather(seqs))
             self.stats["prefill_tokens"] += int(x.ids.numel())
             self._sample_first(seqs, logits)
             return
@@ -350,7 +383,7 @@ class LLMEngine:
             # tensor parallel: all passes layer-major, each pass's all-reduces under the next one's GEMMs
             inputs = [self._pass_inputs(part, spans, paged=True) for part, spans in passes]
             logits = self.model.prefill_passes(inputs, self.state.block_tables, self.kv.k, self.kv.v,
-                                               gather=not self.model.tp_sampling)
+                                               gather=self._gather(passes[-1][0]))
             self.stats["prefill_tokens"] += sum(int(x.ids.numel()) for x in inputs)
             self._sample_first(passes[-1][0], logits)
             return
@@ -388,12 +421,22 @@ class LLMEngine:
 
     def _sample_first(self, seqs: List[_Seq], logits: torch.Tensor) -> None:
         """Sample every sequence's first generated token from its prompt's last row (fed position
-        prompt_len - 1); ``seqs`` occupy consecutive slots."""
+        prompt_len - 1); ``seqs`` occupy consecutive slots.  ``logits`` come from a forward with
+        ``gather=self._gather(seqs)``."""
         st = self.state
         v = st.view(seqs[0].slot, len(seqs))
         v.positions.copy_(torch.tensor([len(s.prompt) - 1 for s in seqs], dtype=torch.int32).to(
             self.device, non_blocking=True))
+        filtered = _any_filtered(seqs)
+        if filtered:
+            self.stats["filtered_steps"] += 1  # the first token is filtered like every other
+        v.filtered = filtered
         self._sample(logits, v)
+
+    def _gather(self, seqs: Sequence[_Seq]) -> bool:
+        """Whether the forward that feeds these sequences' sampler gathers the logits over the TP group: always
+        without vocab-parallel sampling, and for a filtered batch (the filter takes whole rows)."""
+        return not self.model.tp_sampling or _any_filtered(seqs)
 
     def _prefill_pass(self, seqs: List[_Seq], spans, paged: bool, final: bool = True) -> None:
         """One packed forward over prompt slices ``spans`` [(start, end)] of ``seqs``; on the final pass,
@@ -401,40 +444,55 @@ class LLMEngine:
         x = self._pass_inputs(seqs, spans, paged)
         logits = self.model.prefill(x.ids, x.positions, x.seq_idx, x.cu_seqlens, x.last_rows, self.state.block_tables,
                                     self.kv.k, self.kv.v, seqlens=x.seqlens, items=x.items,
-                                    gather=not self.model.tp_sampling, paged=x.paged, logits=final)
+                                    gather=self._gather(seqs), paged=x.paged, logits=final)
         self.stats["prefill_tokens"] += int(x.ids.numel())
         if final:
             self._sample_first(seqs, logits)
 
     # ------------------------------------------------------------------ decode
     def _sample(self, logits: torch.Tensor, st_view) -> None:
-        if self.model.tp_sampling:  # local vocab shard + cross-rank max of the 8-byte Gumbel keys
+        """``st_view.filtered``: some row has a top-k / top-p filter.  Such a batch samples from whole rows
+        (gathered on a vocab-parallel engine) with the single-GPU filtered sampler, the same on every rank."""
+        if st_view.filtered:
+            ops.sample(logits, st_view, filtered=True)
+        elif self.model.tp_sampling:  # local vocab shard + cross-rank max of the 8-byte Gumbel keys
             ops.sample_tp(logits, st_view, self.model.vocab_offset, self.model.custom_ar.max_u64_)
         else:
             ops.sample(logits, st_view)
 
-    def _decode_once(self, B: int) -> None:
+    def _decode_once(self, B: int, filtered: bool = False) -> None:
         st = self.state
         logits = self.model.decode(st.next_ids[:B], st.positions[:B], st.seq_idx[:B], st.block_tables[:B],
                                    self.kv.k, self.kv.v, workspace=self._workspace(B),
-                                   gather=not self.model.tp_sampling)
-        self._sample(logits, st.view(0, B))
+                                   gather=filtered or not self.model.tp_sampling)
+        v = st.view(0, B)
+        v.filtered = filtered
+        self._sample(logits, v)
 
-    def _decode_steps(self, B: int, steps: int) -> None:
+    def _decode_steps(self, B: int, steps: int, filtered: bool = False) -> None:
+        if filtered:
+            self.stats["filtered_steps"] += steps
         if self._fault_delay is not None and int(self._fault_delay[0]) == self.model.tp_rank \
                 and self.model.custom_ar is not None:
             delay, self._fault_delay = self._fault_delay[1], None  # once
             log.warning("fault injection: TP rank %d sleeps %.1f s before a decode window", self.model.tp_rank, delay)
             time.sleep(delay)
-        if not self.use_graphs:
+        if not self.use_graphs or (filtered and self.model.tp_sampling):
+            # a filtered step of a vocab-parallel engine gathers the logits on RCCL, which stays outside
+            # any capture: it runs eagerly
             for _ in range(steps):
-                self._decode_once(B)
+                self._decode_once(B, filtered)
             return
-        g = self._graphs.get((B, self._ctx_cls))
+        g = self._graphs.get(self._graph_key(B, filtered))
         if g is None:
-            g = self._capture(B)
+            g = self._capture(B, filtered)
         for _ in range(steps):
             g.replay()
+
+    def _graph_key(self, B: int, filtered: bool) -> tuple:
+        """Key of a decode graph: (bucket, context class), and (bucket, context class, True) for the graph
+        whose sampler filters (captured on first use; ``capture_graphs`` captures the unfiltered ones)."""
+        return (B, self._ctx_cls, True) if filtered else (B, self._ctx_cls)
 
     def capture_graphs(self, max_batch: Optional[int] = None) -> int:
         """Capture the decode hipGraph of every batch bucket up to ``max_batch`` now (engine start-up,
@@ -460,7 +518,7 @@ class LLMEngine:
         self._sync()
         return n
 
-    def _capture(self, B: int):
+    def _capture(self, B: int, filtered: bool = False):
         # snapshot state rows the warm-up step will advance, run it eagerly once (lazy kernel-library
         # load, workspace and split-K ticket allocation), restore, then capture.
         st = self.state
@@ -468,17 +526,17 @@ class LLMEngine:
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
-            self._decode_once(B)
+            self._decode_once(B, filtered)  # (a filtered warm-up also allocates the filter workspace)
         torch.cuda.current_stream(self.device).wait_stream(s)
         for f, t in snap.items():
             getattr(st, f)[:B].copy_(t)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._decode_once(B)
+            self._decode_once(B, filtered)
         # capture does not execute; restore anyway in case the backend ran the work
         for f, t in snap.items():
             getattr(st, f)[:B].copy_(t)
-        self._graphs[(B, self._ctx_cls)] = g
+        self._graphs[self._graph_key(B, filtered)] = g
         self.stats["graph_captures"] += 1
         return g
 
@@ -506,6 +564,8 @@ class LLMEngine:
         summarised)"""
         if len(prompts) != len(params):
             raise ValueError("prompts and params differ in length")
+        for sp in params:
+            sp.validate()
         eos = list(self.state.eos_ids)
         if ignore_eos:  # device-side stop set: captured graphs see it at replay (sampler.hip EOS_SLOTS)
             self.state.set_eos([])
@@ -575,7 +635,8 @@ class LLMEngine:
                              % (len(p), mn, self.max_model_len))
         if max(p) >= self.cfg.vocab_size or min(p) < 0:
             raise ValueError("token id out of range")
-        return _Seq(i, p, SamplingParams(mn, sp.temperature, sp.seed), imported=imported)
+        sp.validate()
+        return _Seq(i, p, replace(sp, max_new_tokens=mn), imported=imported)
 
     def _fit_ctx_class(self, seqs: Sequence[_Seq]) -> None:
         """Decode attention split plan (graphs are keyed by it) for the longest sequence in flight."""
@@ -638,7 +699,7 @@ class LLMEngine:
                 t0 = time.perf_counter()
                 if t_window_end is not None:  # host work + prefill between two windows of running rows
                     self.stats["max_window_gap_s"] = max(self.stats.get("max_window_gap_s", 0.0), t0 - t_window_end)
-                self._decode_steps(B, steps)
+                self._decode_steps(B, steps, _any_filtered(active))
                 self._sync()
                 t_window_end = time.perf_counter()
                 self.stats["decode_s"] += t_window_end - t0
@@ -731,6 +792,8 @@ class LLMEngine:
             st.done[s.slot] = 0
             st.temps[s.slot] = float(s.params.temperature)
             st.seeds[s.slot] = int(s.params.seed)
+            st.top_k[s.slot] = min(int(s.params.top_k), _I32_MAX)
+            st.top_p[s.slot] = float(s.params.top_p)
             st.result[s.slot] = 0
             if s.imported is not None:  # no forward pass: KV + first token come from elsewhere
                 self._install(s)
@@ -792,6 +855,8 @@ class LLMEngine:
         st.done[s.slot] = 0
         st.temps[s.slot] = float(s.params.temperature)
         st.seeds[s.slot] = int(s.params.seed)
+        st.top_k[s.slot] = min(int(s.params.top_k), _I32_MAX)
+        st.top_p[s.slot] = float(s.params.top_p)
         st.result[s.slot] = 0
 
     def _interleaved_pass(self, prefilling: List[_Seq], active: List[_Seq], max_parts: Optional[int] = None) -> None:
@@ -817,7 +882,8 @@ class LLMEngine:
                                   sample=final)
             logits = self.model.prefill(x.ids, x.positions, x.seq_idx, x.cu_seqlens, x.last_rows, self.pf_tables,
                                         self.kv.k, self.kv.v, seqlens=x.seqlens, items=x.items,
-                                        gather=not self.model.tp_sampling, paged=x.paged, logits=any(final))
+                                        gather=self._gather([s for s, f in zip(part, final) if f]), paged=x.paged,
+                                        logits=any(final))
         except torch.OutOfMemoryError:
             # nothing of this pass is committed yet (spans are popped and slots taken only below; the K/V
             # rows it may have written are rewritten by the retry)
@@ -915,7 +981,7 @@ class LLMEngine:
                 chunks[s.rid] = [torch.stack([k[:, :, g * hl:(g + 1) * hl], v[:, :, g * hl:(g + 1) * hl]])
                                  .reshape(-1) for g in range(groups)]
 
-        one = [SamplingParams(1, p.temperature, p.seed) for p in params]
+        one = [replace(p, max_new_tokens=1) for p in params]
         outs = self.generate(prompts, one, ignore_eos=ignore_eos, on_prefill=grab)
         firsts = [o.token_ids[0] for o in outs]
         packs = [torch.cat([chunks[i][g] for i in range(len(prompts))]) if prompts else
@@ -962,7 +1028,7 @@ class LLMEngine:
         import torch.distributed as dist
         if self.model.tp_size != 1 or self.model.hkv % world or self.kv.fp8:
             raise ValueError("prefill_export_cp needs a TP=1 bf16-KV engine and Hkv divisible by %d" % world)
-        s = self._new_seq(0, prompt, SamplingParams(1, params.temperature, params.seed))
+        s = self._new_seq(0, prompt, replace(params, max_new_tokens=1))
         n = len(s.prompt)
         if n < 2 * world:
             raise ValueError("prompt of %d tokens is too short for context parallelism over %d ranks" % (n, world))
@@ -978,6 +1044,7 @@ class LLMEngine:
             st.block_tables[0].copy_(row.to(dev, non_blocking=True))
             st.max_new[0], st.gen_count[0], st.done[0], st.result[0] = 1, 0, 0, 0
             st.temps[0], st.seeds[0] = float(params.temperature), int(params.seed)
+            st.top_k[0], st.top_p[0] = min(int(params.top_k), _I32_MAX), float(params.top_p)
             slices = self.cp_slices(n, world)
             mine = [(b, e) for b, e in slices[rank] if e > b]
             if len(mine) != len(slices[rank]):  # n >= 2 world: every zigzag chunk holds a token

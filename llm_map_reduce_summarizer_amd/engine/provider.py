@@ -53,7 +53,7 @@ from typing import Any, Dict, List, Optional, Sequence
 
 from ..config import LLMConfig
 from ..parallel import dist as pdist
-from ..pipeline.providers import GenRequest, GenResult, Provider
+from ..pipeline.providers import GenRequest, GenResult, Provider, request_filters
 from .chat import render_chat, render_messages
 from .tokenizer import get_tokenizer
 
@@ -66,6 +66,14 @@ def _req_seed(base: int, req: GenRequest) -> int:
         key += "|" + json.dumps(req.messages, sort_keys=True)
     h = hashlib.sha1(key.encode("utf-8")).digest()
     return int.from_bytes(h[:8], "little") & ((1 << 62) - 1)
+
+
+def sampling_params(req: GenRequest, base_seed: int, config=None):
+    """The engine's SamplingParams of one request: its budget and temperature, the seed derived from
+    its text, and its top-k / top-p filters (the request's own, else $TOP_K / $TOP_P of ``config``)."""
+    from .engine import SamplingParams
+    top_k, top_p = request_filters(req, config)
+    return SamplingParams(req.max_tokens, req.temperature, _req_seed(base_seed, req), top_k=top_k, top_p=top_p)
 
 
 def parse_parallel(spec: str, world: int) -> Dict[str, int]:
@@ -591,8 +599,7 @@ class LocalEngineProvider(Provider):
         """TP=k engines over every request (default k = world: one engine, every rank runs every request);
         ranks agree on ok / error before and after, so a rank-local error (raised before the sharded
         forward) fails the stage on every rank alike."""
-        from .engine import SamplingParams
-        sp = [SamplingParams(r.max_tokens, r.temperature, _req_seed(self.seed, r)) for r in reqs]
+        sp = [sampling_params(r, self.seed, self.config) for r in reqs]
         k = k or self.par.world
         err = None
         try:
@@ -617,7 +624,6 @@ class LocalEngineProvider(Provider):
                           extra={"finish_reason": o.finish_reason}) for o in outs]
 
     async def generate_batch(self, reqs: Sequence[GenRequest]) -> List[GenResult]:
-        from .engine import SamplingParams
         t0 = time.perf_counter()
         prompts = [self.encode_request(r) for r in reqs]
         stage = reqs[0].stage if reqs else "map"
@@ -655,8 +661,7 @@ class LocalEngineProvider(Provider):
                     self._maybe_fault()
                 outs = self.engine.generate(
                     [prompts[i] for i in mine],
-                    [SamplingParams(reqs[i].max_tokens, reqs[i].temperature, _req_seed(self.seed, reqs[i]))
-                     for i in mine],
+                    [sampling_params(reqs[i], self.seed, self.config) for i in mine],
                     ignore_eos=self.ignore_eos)
                 for i, o in zip(mine, outs):
                     local.append({"i": i, "text": self.tokenizer.decode(o.token_ids), "pt": o.prompt_len,
@@ -695,7 +700,6 @@ class LocalEngineProvider(Provider):
         the end (every rank enters it, errors included).  Returns ``(first, second)`` result lists
         (second[g] None when build returned None), or None when this job runs stages on a TP engine
         (the caller then falls back to two barrier-separated generates)."""
-        from .engine import SamplingParams
         if self.par.tp > 1 or (self.par.world > 1 and self.parallel != "dp"):
             return None
         t0 = time.perf_counter()
@@ -741,16 +745,14 @@ class LocalEngineProvider(Provider):
                     continue
                 fed.append(g)
                 fed_mt[g] = r2.max_tokens
-                new.append((self.encode_request(r2),
-                            SamplingParams(r2.max_tokens, r2.temperature, _req_seed(self.seed, r2))))
+                new.append((self.encode_request(r2), sampling_params(r2, self.seed, self.config)))
             return new
 
         try:
             if mine:
                 self._maybe_fault()
                 self.engine.generate([prompts[i] for i in mine],
-                                     [SamplingParams(reqs[i].max_tokens, reqs[i].temperature,
-                                                     _req_seed(self.seed, reqs[i])) for i in mine],
+                                     [sampling_params(reqs[i], self.seed, self.config) for i in mine],
                                      ignore_eos=self.ignore_eos, feeder=feeder)
         except Exception as e:  # noqa: BLE001 -- never skip the all-gather below: the peers are in it
             msg = "rank %d: %s: %s" % (self.par.rank, type(e).__name__, e)

@@ -216,12 +216,20 @@ def attn_decode(q, kcache, vcache, block_tables, positions, hq, hkv, d, page, sc
     return reference.attn_decode(q, kcache, vcache, block_tables, positions, hq, hkv, d, page, scale, out)
 
 
-def sample(logits, st):
+def sample(logits, st, filtered=False):
+    """Sample one token per row into decode state ``st``.  ``filtered``: some row may carry a top-k /
+    top-p filter (``st.top_k`` / ``st.top_p``); every row's threshold is computed first (``st.thresh``,
+    reference.nucleus_threshold) and tokens below it are left out.  Rows without a filter sample exactly
+    as with ``filtered`` False."""
     if _use_hip(logits):
         from . import hip
-        return hip.sample(logits, st)
+        return hip.sample(logits, st, filtered=filtered)
     n = logits.shape[0]
-    toks = reference.sample_tokens(logits, st.temps[:n], st.seeds[:n], st.positions[:n])
+    thresh = None
+    if filtered:
+        st.thresh[:n] = reference.nucleus_threshold(logits, st.temps[:n], st.top_k[:n], st.top_p[:n])
+        thresh = st.thresh[:n]
+    toks = reference.sample_tokens(logits, st.temps[:n], st.seeds[:n], st.positions[:n], thresh)
     reference.sample_finish(toks, st)
 
 

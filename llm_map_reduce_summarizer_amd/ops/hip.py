@@ -58,6 +58,9 @@ _SIGS = {
                    _c_int, _vp],
     "mrsum_sample": [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _vp, _vp,
                      _vp],
+    "mrsum_sample_thresh": [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mrsum_sample_filtered": [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                              _vp, _vp, _c_int, _vp, _vp, _vp],
 }
 
 _fns = {}
@@ -570,14 +573,79 @@ def _eos_ok(st) -> None:
          "sample: eos must be 4 int32 device slots")
 
 
-def sample(logits: torch.Tensor, st) -> None:
-    """Sample one token per row of ``logits`` into decode state ``st`` (see engine.state)."""
+FILTER_ROW = 65536 + 1024  # sampler.hip: per row one u32 count per bf16 bit pattern + one per 64-bin chunk
+
+
+class FilterWorkspace:
+    """The top-k / top-p filter's per-row histograms (sampler.hip): ``rows`` x 66560 u32, 260 KiB per row,
+    allocated on first filtered use -- never inside a graph capture, where allocating is an error (the
+    engine's warm-up step before a capture makes the first use)."""
+
+    def __init__(self, rows: int, device):
+        self.rows, self.device, self._hist = int(rows), device, None
+
+    def hist(self, B: int) -> torch.Tensor:
+        if self._hist is None or self._hist.shape[0] < B:
+            _req(not torch.cuda.is_current_stream_capturing(),
+                 "sample: the filter workspace must exist before a graph capture")
+            self._hist = torch.empty(max(self.rows, B), FILTER_ROW, dtype=torch.int32, device=self.device)
+        return self._hist
+
+
+_filter_ws = {}
+
+
+def _filter_hist(st, B: int, device) -> torch.Tensor:
+    ws = getattr(st, "filter_ws", None)
+    if ws is None:  # a bare state object (tests, tools): one workspace per device
+        ws = _filter_ws.get(str(device))
+        if ws is None:
+            ws = _filter_ws[str(device)] = FilterWorkspace(B, device)
+    return ws.hist(B)
+
+
+def _filter_fields_ok(st, B: int) -> None:
+    _req(st.top_k.is_cuda and st.top_k.dtype == torch.int32 and st.top_k.is_contiguous() and st.top_k.numel() >= B
+         and st.top_p.is_cuda and st.top_p.dtype == torch.float32 and st.top_p.is_contiguous()
+         and st.top_p.numel() >= B and st.thresh.is_cuda and st.thresh.dtype == torch.float32
+         and st.thresh.is_contiguous() and st.thresh.numel() >= B and st.done.numel() >= B,
+         "sample: top_k (int32) / top_p (float32) / thresh (float32) must be contiguous device rows of the batch")
+
+
+def sample_thresholds(logits: torch.Tensor, st) -> torch.Tensor:
+    """The filter's thresholds alone: ``st.thresh[:B]`` = reference.nucleus_threshold of every row (-inf
+    for rows without a filter, greedy rows and done rows)."""
+    _bf16_cuda(logits)
+    _rows_ok(logits)
+    B, V = logits.shape
+    _filter_fields_ok(st, B)
+    hist = _filter_hist(st, B, logits.device)
+    _check(_fn("mrsum_sample_thresh")(_p(logits), logits.stride(0), B, V, _p(st.temps), _p(st.top_k), _p(st.top_p),
+                                      _p(st.done), _p(st.thresh), _p(hist), _stream()), "sample_thresh")
+    return st.thresh[:B]
+
+
+def sample(logits: torch.Tensor, st, filtered: bool = False) -> None:
+    """Sample one token per row of ``logits`` into decode state ``st`` (see engine.state).  ``filtered``
+    and ``st`` carrying ``top_k`` / ``top_p`` / ``thresh`` rows: the top-k / top-p path (histogram,
+    threshold, Gumbel-max over the kept tokens); otherwise the plain sampler, the same launch as ever."""
     _bf16_cuda(logits)
     _rows_ok(logits)
     B, V = logits.shape
     _req(st.temps.numel() >= B and st.next_ids.numel() >= B and st.out_tokens.shape[0] >= B,
          "sample: state smaller than batch")
     _eos_ok(st)
+    if filtered:
+        _req(all(hasattr(st, f) for f in ("top_k", "top_p", "thresh")),
+             "sample: a filtered batch needs top_k / top_p / thresh rows in the state")
+        _filter_fields_ok(st, B)
+        hist = _filter_hist(st, B, logits.device)
+        _check(_fn("mrsum_sample_filtered")(_p(logits), logits.stride(0), B, V, _p(st.temps), _p(st.seeds),
+                                            _p(st.positions), _p(st.top_k), _p(st.top_p), _p(st.thresh), _p(hist),
+                                            _p(st.result), _p(st.next_ids), _p(st.positions), _p(st.gen_count),
+                                            _p(st.max_new), _p(st.out_tokens), st.out_tokens.stride(0), _p(st.done),
+                                            _p(st.eos), _stream()), "sample_filtered")
+        return
     _check(_fn("mrsum_sample")(_p(logits), logits.stride(0), B, V, _p(st.temps), _p(st.seeds), _p(st.positions),
                                _p(st.result), _p(st.next_ids), _p(st.positions), _p(st.gen_count), _p(st.max_new),
                                _p(st.out_tokens), st.out_tokens.stride(0), _p(st.done), _p(st.eos),

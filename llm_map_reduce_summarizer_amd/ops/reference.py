@@ -367,16 +367,75 @@ def gumbel_noise(seed: int, position: int, vocab: int, device=None) -> torch.Ten
     return (-torch.log(-torch.log(u))).float().to(device)
 
 
+def nucleus_levels(row: torch.Tensor, temp: float):
+    """The levels of one logits row for the top-k / top-p rule: ``(values, counts, weights)``, float64 /
+    int64 / float64, values descending.  A level is one distinct stored value (-0 and +0 are one level);
+    its weight is count * exp((value - top value) / temp).  NaNs are no level."""
+    r = row.detach().double().cpu().reshape(-1)
+    r = r[~torch.isnan(r)] + 0.0  # -0.0 + 0.0 = +0.0
+    vals, counts = torch.unique(r, return_counts=True)
+    vals, counts = vals.flip(0), counts.flip(0)
+    if vals.numel() == 0:
+        return vals, counts, vals.clone()
+    d = (vals - vals[0]) / temp
+    d = torch.where(vals == vals[0], torch.zeros_like(d), d)  # inf - inf
+    return vals, counts, counts.double() * torch.exp(d)
+
+
+def nucleus_cut(row: torch.Tensor, temp: float, top_k: int, top_p: float):
+    """``(threshold, margin)`` of one row, in float64: the value of the last kept level (-inf for a row
+    without a filter or with temp <= 0) and the relative distance of p * Z from the cumulative mass on
+    either side of the top-p cut (inf where top-p decides nothing)."""
+    V = row.numel()
+    if temp <= 0 or (top_k <= 0 and top_p >= 1.0):
+        return float("-inf"), float("inf")
+    vals, counts, w = nucleus_levels(row, temp)
+    if vals.numel() == 0:
+        return float("-inf"), float("inf")
+    last = vals.numel() - 1
+    jk = last
+    if 0 < top_k < V:
+        jk = min(last, int(torch.searchsorted(torch.cumsum(counts, 0), top_k)))
+    j, margin = jk, float("inf")
+    if top_p < 1.0:
+        cum = torch.cumsum(w[:jk + 1], 0)
+        target = top_p * float(cum[-1])
+        j = min(jk, int(torch.searchsorted(cum, torch.tensor(target, dtype=torch.float64))))
+        below = float(cum[j - 1]) if j > 0 else 0.0
+        margin = min(float(cum[j]) - target, target - below) / target
+    return float(vals[j]), margin
+
+
+def nucleus_threshold(logits: torch.Tensor, temps, top_k, top_p) -> torch.Tensor:
+    """Per-row top-k / top-p threshold, fp32 [B]: a token is kept iff its logit >= the threshold.
+
+    The levels of a row are its distinct stored values, descending (v1 > v2 > ..., counts n_i, -0 = +0),
+    with weights w_i = n_i exp((v_i - v1) / temp).  top-k keeps the levels up to the first whose
+    cumulative count reaches k (all of them for k = 0 or k >= V); top-p, over that set, keeps the levels
+    up to the first whose cumulative weight reaches p times the set's total.  Whole levels are kept, so
+    ties at the cut all stay.  temp <= 0, or k = 0 with p >= 1: -inf (no filter).  Computed in float64;
+    sampler.hip's filter kernels match it."""
+    B = logits.shape[0]
+    out = torch.empty(B, dtype=torch.float32)
+    for b in range(B):
+        out[b] = nucleus_cut(logits[b], float(temps[b]), int(top_k[b]), float(top_p[b]))[0]
+    return out
+
+
 def sample_tokens(logits: torch.Tensor, temps: torch.Tensor, seeds: torch.Tensor,
-                  positions: torch.Tensor) -> torch.Tensor:
-    """Gumbel-max sampling (argmax when temperature <= 0); ties -> lowest id."""
+                  positions: torch.Tensor, thresh: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gumbel-max sampling (argmax when temperature <= 0); ties -> lowest id.  ``thresh`` (fp32 [B],
+    nucleus_threshold): tokens of row b with a logit below thresh[b] are left out."""
     B, V = logits.shape
     out = torch.empty(B, dtype=torch.int32)
     for b in range(B):
         row = logits[b].float().cpu()
         t = float(temps[b])
         if t > 0:
+            keep = None if thresh is None else row >= float(thresh[b])
             row = row / t + gumbel_noise(int(seeds[b]), int(positions[b]), V)
+            if keep is not None:
+                row = torch.where(keep, row, torch.full_like(row, float("-inf")))
         out[b] = int(torch.argmax(row))
     return out.to(logits.device)
 

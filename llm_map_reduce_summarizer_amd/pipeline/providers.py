@@ -24,7 +24,7 @@ import hashlib
 import logging
 import random
 from dataclasses import dataclass, field
-from typing import Any, Dict, List, Optional, Sequence
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 from ..config import LLMConfig
 
@@ -42,6 +42,16 @@ class GenRequest:
     # a whole chat ([{"role": "system" | "user" | "assistant", "content": str}, ...]) instead of the
     # reference's [system?, user] pair -- the HTTP front-end (serve.py) passes multi-turn requests here
     messages: Optional[List[Dict[str, str]]] = None
+    # sampling filters; None = the configured default ($TOP_K / $TOP_P: 0 / 1.0 = off)
+    top_k: Optional[int] = None
+    top_p: Optional[float] = None
+
+
+def request_filters(req: GenRequest, config: Optional[LLMConfig]) -> Tuple[int, float]:
+    """(top_k, top_p) of a request: its own values, else the configured defaults (0 / 1.0 = off)."""
+    k = req.top_k if req.top_k is not None else getattr(config, "TOP_K", 0)
+    p = req.top_p if req.top_p is not None else getattr(config, "TOP_P", 1.0)
+    return int(k), float(p)
 
 
 @dataclass
@@ -182,8 +192,11 @@ class OpenAIProvider(_HTTPProvider):
             headers["OpenAI-Organization"] = self.config.OPENAI_ORG_ID
         msgs = ([{"role": "system", "content": req.system}] if req.system else []) + [
             {"role": "user", "content": req.user}]
-        data = await self._post(headers, {"model": self.model, "messages": msgs, "temperature": req.temperature,
-                                          "max_tokens": req.max_tokens})
+        body = {"model": self.model, "messages": msgs, "temperature": req.temperature, "max_tokens": req.max_tokens}
+        _k, top_p = request_filters(req, self.config)  # the OpenAI API has no top_k
+        if top_p < 1.0:
+            body["top_p"] = top_p
+        data = await self._post(headers, body)
         usage = data.get("usage", {})
         pt, ct = usage.get("prompt_tokens", 0), usage.get("completion_tokens", 0)
         # reference llm_executor.py:310-317
@@ -205,6 +218,11 @@ class AnthropicProvider(_HTTPProvider):
                                 "temperature": req.temperature, "max_tokens": req.max_tokens}
         if req.system:
             body["system"] = req.system
+        top_k, top_p = request_filters(req, self.config)
+        if top_p < 1.0:
+            body["top_p"] = top_p
+        if top_k > 0:
+            body["top_k"] = top_k
         data = await self._post(headers, body)
         text = data["content"][0]["text"]
         usage = data.get("usage") or {}

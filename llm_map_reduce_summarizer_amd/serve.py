@@ -13,7 +13,9 @@ Endpoints: ``POST /v1/chat/completions``, ``POST /v1/messages``, ``GET /v1/model
 ``GET /metrics`` (Prometheus text).  ``stream: true`` on the chat endpoint streams
 ``chat.completion.chunk`` events as the engine produces tokens (every host sync point, 16 decode steps)
 on a single-process engine, the whole completion as one event under torchrun; Anthropic streaming gets the
-message as one event.  Stop sequences and n > 1 are not supported (400).
+message as one event.  ``top_p`` (both endpoints) and ``top_k`` (``/v1/messages``; on the chat endpoint as
+the common extension) restrict the sample on the GPU (sampler.hip's filter kernels); a value out of range
+or not a number is a 400.  Stop sequences and n > 1 are not supported (400).
 
 Batching: HTTP handlers only enqueue; one engine thread owns the engine.  Single process
 (``ContinuousBatcher``): the first requests start a generate and every request that arrives while it runs
@@ -81,6 +83,22 @@ def _common(body: Dict[str, Any], default_temp: float) -> Tuple[int, float]:
     return max_tokens, float(default_temp if temp is None else temp)
 
 
+def _filters(body: Dict[str, Any]) -> Dict[str, Any]:
+    """``top_p`` / ``top_k`` of a request body as GenRequest fields (absent or null: the server's default).
+    ``top_k`` is Anthropic's field and the common extension of OpenAI-compatible servers."""
+    out: Dict[str, Any] = {}
+    p, k = body.get("top_p"), body.get("top_k")
+    if p is not None:
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 < float(p) <= 1.0:
+            raise BadRequest("top_p must be a number in (0, 1]")
+        out["top_p"] = float(p)
+    if k is not None:
+        if isinstance(k, bool) or not isinstance(k, (int, float)) or k != int(k) or k < 0:
+            raise BadRequest("top_k must be an integer >= 0")
+        out["top_k"] = int(k)
+    return out
+
+
 def openai_request(body: Dict[str, Any], default_temp: float = 1.0) -> GenRequest:
     """GenRequest of an OpenAI ``/v1/chat/completions`` body.  A [system?, user] chat keeps the
     reference's request shape (same prompt rendering and seed as the in-process provider)."""
@@ -96,12 +114,13 @@ def openai_request(body: Dict[str, Any], default_temp: float = 1.0) -> GenReques
             raise BadRequest("unsupported message role %r" % role)
         turns.append({"role": role, "content": _text(m.get("content", ""))})
     max_tokens, temp = _common(body, default_temp)
+    filters = _filters(body)
     roles = [t["role"] for t in turns]
     if roles in (["user"], ["system", "user"]):
         return GenRequest(user=turns[-1]["content"], system=turns[0]["content"] if len(turns) == 2 else None,
-                          max_tokens=max_tokens, temperature=temp, stage="serve")
+                          max_tokens=max_tokens, temperature=temp, stage="serve", **filters)
     return GenRequest(user=turns[-1]["content"], max_tokens=max_tokens, temperature=temp, stage="serve",
-                      messages=turns)
+                      messages=turns, **filters)
 
 
 def anthropic_request(body: Dict[str, Any], default_temp: float = 1.0) -> GenRequest:
@@ -118,13 +137,14 @@ def anthropic_request(body: Dict[str, Any], default_temp: float = 1.0) -> GenReq
             raise BadRequest("unsupported message role %r" % role)
         turns.append({"role": role, "content": _text(m.get("content", ""))})
     max_tokens, temp = _common(body, default_temp)
+    filters = _filters(body)
     if [t["role"] for t in turns[-1:]] != ["user"]:
         raise BadRequest("the last message must be from the user")
     if len(msgs) == 1:
         return GenRequest(user=turns[-1]["content"], system=system, max_tokens=max_tokens, temperature=temp,
-                          stage="serve")
+                          stage="serve", **filters)
     return GenRequest(user=turns[-1]["content"], max_tokens=max_tokens, temperature=temp, stage="serve",
-                      messages=turns)
+                      messages=turns, **filters)
 
 
 def _finish(res: GenResult) -> str:
@@ -284,8 +304,7 @@ class ContinuousBatcher(Batcher):
             return
 
     def loop(self) -> None:
-        from .engine.engine import SamplingParams
-        from .engine.provider import _req_seed
+        from .engine.provider import sampling_params
         prov = self.provider
         while not self.stop.is_set():
             items = self._collect(0.1)
@@ -310,7 +329,7 @@ class ContinuousBatcher(Batcher):
                     if len(it) > 3:
                         sent[nxt[0]] = 0
                     nxt[0] += 1
-                    out.append((ids, SamplingParams(req.max_tokens, req.temperature, _req_seed(prov.seed, req))))
+                    out.append((ids, sampling_params(req, prov.seed, prov.config)))
                     self.stats["requests"] += 1
                 return out
 

@@ -1,0 +1,108 @@
+#!/usr/bin/env python3
+"""Cost of the sampler launch (ops.hip.sample) without and with the top-k / top-p filter, at decode batch
+sizes over the real vocabulary.
+
+Every timed launch is preceded by a rewrite of the logits (a device copy from one of several source
+buffers), as the LM head rewrites them before every decode step: the histogram kernel then does not read
+rows that an earlier iteration of this loop left in cache.  Device events time N x (rewrite + sample) and
+N x (rewrite) back to back; the difference / N is the sampler's cost.  Modes: ``plain`` (the unfiltered
+launch), ``all`` (every row top_k=40 top_p=0.9), ``one`` (row 0 filtered, the others not: they exit the
+filter kernels at once), ``thresh`` (the two filter kernels alone, every row filtered).
+
+    python tools/bench_sampler.py --bs 1,10,39 > profiles/sampler_filter.jsonl
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ap.add_argument("--bs", default="1,10,39")
+ap.add_argument("--vocab", type=int, default=128256)
+ap.add_argument("--iters", type=int, default=200)
+ap.add_argument("--repeats", type=int, default=5)
+ap.add_argument("--temperature", type=float, default=0.3)
+ap.add_argument("--scale", type=float, default=3.0, help="std of the random logits")
+args = ap.parse_args()
+sys.path.insert(0, os.path.abspath(args.tree))
+
+import torch  # noqa: E402
+
+from llm_map_reduce_summarizer_amd.ops import hip  # noqa: E402
+
+if not torch.cuda.is_available():
+    raise SystemExit("bench_sampler needs a GPU")
+dev = "cuda:0"
+NSRC = 4
+
+
+class State:
+    def __init__(self, B, cap, top_k, top_p):
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.next_ids = torch.zeros(B, **i32)
+        self.positions = torch.zeros(B, **i32)
+        self.gen_count = torch.zeros(B, **i32)
+        self.max_new = torch.full((B,), cap, **i32)
+        self.out_tokens = torch.zeros(B, cap, **i32)
+        self.done = torch.zeros(B, **i32)
+        self.result = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.temps = torch.full((B,), args.temperature, dtype=torch.float32, device=dev)
+        self.seeds = torch.arange(B, dtype=torch.int64, device=dev)
+        self.eos = torch.full((4,), -1, **i32)
+        self.top_k = torch.tensor(top_k, **i32)
+        self.top_p = torch.tensor(top_p, dtype=torch.float32, device=dev)
+        self.thresh = torch.zeros(B, dtype=torch.float32, device=dev)
+
+
+def timed(fn, n):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for i in range(n):
+        fn(i)
+    e.record()
+    e.synchronize()
+    return s.elapsed_time(e) * 1e3 / n  # us per iteration
+
+
+for B in (int(b) for b in args.bs.split(",")):
+    g = torch.Generator(device="cpu").manual_seed(B)
+    srcs = [(torch.randn(B, args.vocab, generator=g) * args.scale).to(torch.bfloat16).to(dev) for _ in range(NSRC)]
+    logits = torch.empty_like(srcs[0])
+    cap = (args.repeats + 1) * args.iters + 8
+    modes = {
+        "plain": ([0] * B, [1.0] * B),
+        "all": ([40] * B, [0.9] * B),
+        "one": ([40] + [0] * (B - 1), [0.9] + [1.0] * (B - 1)),
+        "thresh": ([40] * B, [0.9] * B),
+    }
+
+    def rewrite(i):
+        logits.copy_(srcs[i % NSRC])
+
+    res = {}
+    for mode, (ks, ps) in modes.items():
+        st = State(B, cap, ks, ps)
+
+        def step(i, st=st, mode=mode):
+            rewrite(i)
+            if mode == "thresh":
+                hip.sample_thresholds(logits, st)
+            else:
+                hip.sample(logits, st, filtered=mode != "plain")
+
+        timed(step, args.iters)  # warm-up (code objects, the filter workspace)
+        # alternate the two loops so a clock or neighbour change hits both
+        d = []
+        for _ in range(args.repeats):
+            d.append(timed(step, args.iters) - timed(rewrite, args.iters))
+        res[mode] = d
+        if mode != "thresh":
+            assert int(st.gen_count.min()) == (args.repeats + 1) * args.iters
+    rec = {"B": B, "V": args.vocab, "temperature": args.temperature, "iters": args.iters, "repeats": args.repeats}
+    for mode, d in res.items():
+        rec[mode + "_us"] = round(statistics.median(d), 2)
+        rec[mode + "_us_min_max"] = [round(min(d), 2), round(max(d), 2)]
+    rec["filter_extra_us"] = round(rec["all_us"] - rec["plain_us"], 2)
+    print(json.dumps(rec), flush=True)
