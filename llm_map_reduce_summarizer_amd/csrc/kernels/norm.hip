@@ -83,9 +83,9 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const bf16* __restrict__ x
         for (int i = 0; i < VPT; ++i) {
             const int c = threadIdx.x + i * 256;
             if (c < nvec) {
-                float y[8];
+                float y[8];  // + 0.f (one fma): -0, a zero x under a negative w, becomes +0 -- byte 0x00, not 0x80
 #pragma unroll
-                for (int j = 0; j < 8; ++j) y[j] = v[i][j] * qi;
+                for (int j = 0; j < 8; ++j) y[j] = v[i][j] * qi + 0.f;
                 int lo = 0, hi = 0;
                 lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], lo, false);
                 lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], lo, true);

@@ -141,7 +141,7 @@ def add_rmsnorm(x: torch.Tensor, residual: torch.Tensor, w: torch.Tensor, eps: f
     _rows_ok(x)
     T, D = x.shape
     _req(residual.shape == (T, D) and residual.is_contiguous(), "add_rmsnorm: residual must be [T, D] contiguous")
-    _req(w.numel() == D and D % 8 == 0 and D <= 16384, "add_rmsnorm: bad weight / D")
+    _req(w.numel() == D and w.is_contiguous() and D % 8 == 0 and D <= 16384, "add_rmsnorm: bad weight / D")
     if out is None:
         out = torch.empty(T, D, dtype=x.dtype, device=x.device)
     _rows_ok(out)
@@ -1103,11 +1103,13 @@ def add_rmsnorm_parts(parts: torch.Tensor, residual: torch.Tensor, w: torch.Tens
          "add_rmsnorm_parts: parts must be fp32 [S, T, D]")
     _bf16_cuda(residual, w)
     S, T, D = parts.shape
-    _req(residual.shape == (T, D) and residual.is_contiguous() and w.numel() == D and D % 8 == 0,
-         "add_rmsnorm_parts: shapes")
+    _req(residual.shape == (T, D) and residual.is_contiguous() and w.numel() == D and w.is_contiguous()
+         and D % 8 == 0 and D <= 16384, "add_rmsnorm_parts: shapes")
     if out is None:
         out = torch.empty(T, D, dtype=residual.dtype, device=residual.device)
+    _bf16_cuda(out)
     _rows_ok(out)
+    _req(out.shape == (T, D), "add_rmsnorm_parts: bad out shape")
     _check(_fn("mrsum_add_rmsnorm_parts")(_p(parts), S, _p(residual), _p(w), _p(out), T, D, out.stride(0), eps,
                                           _stream()), "add_rmsnorm_parts")
     return out
