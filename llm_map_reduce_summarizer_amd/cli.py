@@ -24,6 +24,7 @@ import argparse
 import asyncio
 import json
 import logging
+import math
 import os
 import sys
 from pathlib import Path
@@ -68,6 +69,16 @@ def build_parser() -> argparse.ArgumentParser:
                    help="override $TOP_P: nucleus sampling, map and reduce (0 < p <= 1; 1.0 = off)")
     g.add_argument("--top-k", type=int, default=None,
                    help="override $TOP_K: sample among the k most likely tokens, map and reduce (0 = off)")
+    g.add_argument("--frequency-penalty", type=float, default=None,
+                   help="override $FREQUENCY_PENALTY: subtracted from a token's logit once per time the "
+                        "sequence has generated it, map and reduce (0 = off)")
+    g.add_argument("--presence-penalty", type=float, default=None,
+                   help="override $PRESENCE_PENALTY: subtracted from the logit of every token the sequence "
+                        "has generated, map and reduce (0 = off)")
+    g.add_argument("--repetition-penalty", type=float, default=None,
+                   help="override $REPETITION_PENALTY: divides the positive / multiplies the negative logits "
+                        "of the tokens the sequence has GENERATED (the prompt is not counted, unlike HF / "
+                        "vLLM), map and reduce (> 0; 1.0 = off)")
     g.add_argument("--fault-inject", type=float, default=0.0, help="mock provider: failure probability")
     g.add_argument("--profile", default=None, metavar="DIR",
                    help="torch.profiler trace of the run: DIR/trace_rank{r}.json + top-kernel table")
@@ -138,6 +149,14 @@ def config_from_args(args: argparse.Namespace):
         cfg.TOP_K = args.top_k
     if cfg.TOP_K < 0 or not 0.0 < cfg.TOP_P <= 1.0:
         raise SystemExit("top-k must be >= 0 and top-p in (0, 1], got %r / %r" % (cfg.TOP_K, cfg.TOP_P))
+    for flag, key in (("frequency_penalty", "FREQUENCY_PENALTY"), ("presence_penalty", "PRESENCE_PENALTY"),
+                      ("repetition_penalty", "REPETITION_PENALTY")):
+        if getattr(args, flag, None) is not None:
+            setattr(cfg, key, getattr(args, flag))
+    pens = (cfg.FREQUENCY_PENALTY, cfg.PRESENCE_PENALTY, cfg.REPETITION_PENALTY)
+    if not all(math.isfinite(x) for x in pens) or not cfg.REPETITION_PENALTY > 0:
+        raise SystemExit("frequency / presence penalty must be finite and repetition penalty > 0, got %r / %r / %r"
+                         % pens)
     return cfg
 
 

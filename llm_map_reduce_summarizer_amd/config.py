@@ -65,6 +65,9 @@ class LLMConfig:
         "REDUCE_TEMPERATURE": ("0.2", float),
         # sampling filters of the map and the reduce stage (1.0 / 0 = off)
         "TOP_P": ("1.0", float), "TOP_K": ("0", int),
+        # penalties on the tokens a sequence has generated, map and reduce (0 / 0 / 1 = off)
+        "FREQUENCY_PENALTY": ("0.0", float), "PRESENCE_PENALTY": ("0.0", float),
+        "REPETITION_PENALTY": ("1.0", float),
         # hosted-provider endpoints (new): point the adapters at any compatible server
         "OPENAI_BASE_URL": ("https://api.openai.com/v1", str),
         "ANTHROPIC_BASE_URL": ("https://api.anthropic.com/v1", str),

@@ -256,6 +256,92 @@ __global__ __launch_bounds__(SELECT_THREADS) void filter_select_kernel(const uns
     if (threadIdx.x == 0) thresh[b] = key16_value(cut);
 }
 
+// ------------------------------------------------------------------ repetition / frequency / presence penalties
+// penalize: one workgroup per row rewrites, in place and before the sampler (and the filter) runs, the logits
+//          of the tokens the row has generated so far (ops/reference.py apply_penalties is the definition):
+//          x = rep > 0 ? x / rep : x * rep;  x -= freq * count;  x -= pres;  every step one rounded fp32
+//          operation, stored back as bf16 (RNE).  The counts are a function of out_tokens[b, :gen_count[b]]
+//          alone, rebuilt at every launch: the tokens are reduced to (distinct token, count) in an LDS
+//          open-addressing table (LDS atomics; 2 slots per token at least, multiplicative hash, linear
+//          probing), then every occupied slot rewrites its token's logit -- one thread per distinct token, no
+//          global atomics, no workspace.  A neutral, done or empty row costs one early-exit workgroup.
+//          TABLE = false is the other form of the same reduction, an ownership scan over the staged tokens
+//          (the thread holding a token's first occurrence counts the others): O(gen_count^2 / threads) LDS
+//          reads, kept for the measurement in tools/bench_sampler.py (profiles/sampler_penalties.jsonl).
+constexpr int PEN_THREADS = 512;
+constexpr int PEN_CAP = 4096;            // most generated tokens per row (ops.hip.PENALTY_MAX_TOKENS)
+constexpr int PEN_SLOTS = 2 * PEN_CAP;   // 2 x 32 KiB of LDS: keys + counts
+
+__device__ __forceinline__ void penalize_logit(bf16* p, int count, float rep, float freq, float pres) {
+    // The reference rounds every step, so no product may be fused into the subtraction after it.  The
+    // library is built with -ffp-contract=fast, under which the backend fuses whatever the pragma says:
+    // the empty asm statements make the two products opaque to it.
+#pragma clang fp contract(off)
+    float x = (float)*p;
+    if (rep != 1.f) x = x > 0.f ? x / rep : x * rep;
+    float f = freq * (float)count;
+    asm volatile("" : "+v"(x), "+v"(f));
+    x = x - f;
+    x = x - pres;
+    *p = (bf16)x;
+}
+
+template <bool TABLE>
+__global__ __launch_bounds__(PEN_THREADS) void penalize_kernel(bf16* __restrict__ logits, int ld, int V,
+                                                               int tok_offset, const int* __restrict__ out_tokens,
+                                                               int out_stride, const int* __restrict__ gen_count,
+                                                               const int* __restrict__ done,
+                                                               const float* __restrict__ rep_pen,
+                                                               const float* __restrict__ freq_pen,
+                                                               const float* __restrict__ pres_pen) {
+    __shared__ int s_key[PEN_SLOTS];
+    __shared__ int s_cnt[PEN_SLOTS];
+    const int b = blockIdx.x;
+    const float rep = rep_pen[b], freq = freq_pen[b], pres = pres_pen[b];
+    const int g = min(min(gen_count[b], out_stride), PEN_CAP);  // (the launcher refuses wider token rows)
+    if ((rep == 1.f && freq == 0.f && pres == 0.f) || g <= 0 || (done != nullptr && done[b])) return;  // block-uniform
+    const int* toks = out_tokens + (size_t)b * out_stride;
+    bf16* row = logits + (size_t)b * ld;
+    if constexpr (TABLE) {
+        int lg = 32 - __clz(2 * g - 1);  // slots = 2^lg >= 2 g: the probe of an absent key always ends
+        lg = max(lg, 6);
+        const int slots = 1 << lg;
+        for (int i = threadIdx.x; i < slots; i += PEN_THREADS) { s_key[i] = -1; s_cnt[i] = 0; }
+        __syncthreads();
+        for (int i = threadIdx.x; i < g; i += PEN_THREADS) {
+            const int t = toks[i];
+            if ((unsigned int)t - (unsigned int)tok_offset >= (unsigned int)V) continue;  // another shard's token
+            unsigned int h = ((unsigned int)t * 2654435761u) >> (32 - lg);
+            for (;;) {
+                const int prev = atomicCAS(&s_key[h], -1, t);
+                if (prev == -1 || prev == t) break;
+                h = (h + 1) & (unsigned int)(slots - 1);
+            }
+            atomicAdd(&s_cnt[h], 1);
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < slots; i += PEN_THREADS) {
+            const int t = s_key[i];
+            if (t >= 0) penalize_logit(row + (t - tok_offset), s_cnt[i], rep, freq, pres);
+        }
+    } else {
+        for (int i = threadIdx.x; i < g; i += PEN_THREADS) s_key[i] = toks[i];
+        __syncthreads();
+        for (int i = threadIdx.x; i < g; i += PEN_THREADS) {
+            const int t = s_key[i];
+            if ((unsigned int)t - (unsigned int)tok_offset >= (unsigned int)V) continue;
+            int c = 0;
+            bool first = true;
+            for (int j = 0; j < g; ++j) {
+                const bool same = s_key[j] == t;
+                c += same;
+                first = first && !(same && j < i);
+            }
+            if (first) penalize_logit(row + (t - tok_offset), c, rep, freq, pres);
+        }
+    }
+}
+
 template <bool FILTER>
 __global__ __launch_bounds__(256) void sample_kernel(const bf16* __restrict__ logits, int ld, int V, int tok_offset,
                                                      const float* __restrict__ temps,
@@ -408,5 +494,28 @@ MRSUM_API int mrsum_sample_filtered(const void* logits, int ld, int B, int V, co
     if (e) return e;
     sample_finish_kernel<<<ceil_div(B, 64), 64, 0, s>>>((unsigned long long*)result, next_ids, positions_rw,
                                                         gen_count, max_new, out_tokens, out_stride, done, eos, B);
+    return (int)hipGetLastError();
+}
+
+// Repetition / frequency / presence penalties on the logits rows, in place, ahead of any sampler launch on
+// stream s (capturable).  V / tok_offset: the width and first global token id of the rows (a vocab-parallel
+// rank's shard: tokens of other shards are skipped).  a row holds at most PEN_CAP generated tokens (the
+// Python launcher refuses wider out_tokens rows).  done may be null.
+MRSUM_API int mrsum_penalize(void* logits, int ld, int B, int V, int tok_offset, const int* out_tokens,
+                             int out_stride, const int* gen_count, const int* done, const float* rep,
+                             const float* freq, const float* pres, hipStream_t s) {
+    if (B <= 0) return 0;
+    penalize_kernel<true><<<B, PEN_THREADS, 0, s>>>((bf16*)logits, ld, V, tok_offset, out_tokens, out_stride,
+                                                    gen_count, done, rep, freq, pres);
+    return (int)hipGetLastError();
+}
+
+// The ownership-scan form of the same kernel (measurement and its equality test only).
+MRSUM_API int mrsum_penalize_scan(void* logits, int ld, int B, int V, int tok_offset, const int* out_tokens,
+                                  int out_stride, const int* gen_count, const int* done, const float* rep,
+                                  const float* freq, const float* pres, hipStream_t s) {
+    if (B <= 0) return 0;
+    penalize_kernel<false><<<B, PEN_THREADS, 0, s>>>((bf16*)logits, ld, V, tok_offset, out_tokens, out_stride,
+                                                     gen_count, done, rep, freq, pres);
     return (int)hipGetLastError();
 }

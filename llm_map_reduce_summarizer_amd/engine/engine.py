@@ -22,6 +22,7 @@ every chunk of a rank is in flight at once, bounded only by HBM.
 from __future__ import annotations
 
 import logging
+import math
 import os
 import time
 from dataclasses import dataclass, field, replace
@@ -52,6 +53,11 @@ def _any_filtered(seqs) -> bool:
     return any(s.params.filtered for s in seqs)
 
 
+def _any_penalised(seqs) -> bool:
+    """Whether any of these sequences carries a repetition / frequency / presence penalty."""
+    return any(s.params.penalised for s in seqs)
+
+
 @dataclass
 class SamplingParams:
     max_new_tokens: int = 1000
@@ -59,14 +65,31 @@ class SamplingParams:
     seed: int = 0
     top_k: int = 0  # keep the k most likely tokens (ties at the cut all stay); 0 = off
     top_p: float = 1.0  # nucleus: the smallest top set holding this share of the top-k mass; 1.0 = off
+    # penalties on the tokens the sequence has GENERATED so far, never on the prompt
+    # (ops.reference.apply_penalties): logit -= frequency_penalty * count + presence_penalty, after a
+    # positive logit was divided and a negative one multiplied by repetition_penalty.  0 / 0 / 1 = off
+    frequency_penalty: float = 0.0
+    presence_penalty: float = 0.0
+    repetition_penalty: float = 1.0
 
     @property
     def filtered(self) -> bool:
         """Whether sampling with these parameters is restricted at all (greedy rows never are)."""
         return self.temperature > 0 and (self.top_k > 0 or self.top_p < 1.0)
 
+    @property
+    def penalised(self) -> bool:
+        """Whether these parameters change the logits of tokens already generated (greedy rows included)."""
+        return self.frequency_penalty != 0 or self.presence_penalty != 0 or self.repetition_penalty != 1
+
     def validate(self) -> None:
         k, p = self.top_k, self.top_p
+        for name in ("frequency_penalty", "presence_penalty", "repetition_penalty"):
+            x = getattr(self, name)
+            if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x):
+                raise ValueError("%s must be a finite number, got %r" % (name, x))
+        if not self.repetition_penalty > 0:
+            raise ValueError("repetition_penalty must be > 0, got %r" % (self.repetition_penalty,))
         if isinstance(k, bool) or not isinstance(k, int) or k < 0:
             raise ValueError("top_k must be an integer >= 0, got %r" % (k,))
         if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 < p <= 1.0:
@@ -123,6 +146,11 @@ class DecodeState:
         self.top_k = torch.zeros(max_seqs, **i32)
         self.top_p = torch.ones(max_seqs, dtype=torch.float32, device=device)
         self.thresh = torch.full((max_seqs,), float("-inf"), dtype=torch.float32, device=device)
+        # repetition / frequency / presence penalty of every row (1 / 0 / 0 = off), applied to the logits of
+        # out_tokens[row, :gen_count[row]] before a penalised step samples (ops.reference.apply_penalties)
+        self.rep_pen = torch.ones(max_seqs, dtype=torch.float32, device=device)
+        self.freq_pen = torch.zeros(max_seqs, dtype=torch.float32, device=device)
+        self.pres_pen = torch.zeros(max_seqs, dtype=torch.float32, device=device)
         self.filter_ws = None
         if self.temps.is_cuda:
             from ..ops.hip import FilterWorkspace
@@ -142,7 +170,7 @@ class DecodeState:
         self.eos_ids = ids
 
     _ROW_FIELDS = ("next_ids", "positions", "block_tables", "gen_count", "max_new", "out_tokens", "done", "result",
-                   "temps", "seeds", "top_k", "top_p", "thresh")
+                   "temps", "seeds", "top_k", "top_p", "thresh", "rep_pen", "freq_pen", "pres_pen")
 
     def view(self, start: int, n: int) -> "DecodeState":
         v = object.__new__(DecodeState)
@@ -153,6 +181,7 @@ class DecodeState:
         v.eos, v.eos_ids = self.eos, self.eos_ids
         v.filter_ws = self.filter_ws
         v.filtered = False  # set by the engine on the view of a batch with a top-k / top-p row
+        v.penalised = False  # ... and of a batch with a penalised row
         return v
 
     def move_row(self, src: int, dst: int) -> None:
@@ -166,6 +195,7 @@ class DecodeState:
         self.positions[i] = 0
         self.block_tables[i].zero_()
         self.gen_count[i] = 0
+        self.rep_pen[i], self.freq_pen[i], self.pres_pen[i] = 1.0, 0.0, 0.0
 
 
 class _CPExchange:
@@ -311,7 +341,7 @@ class LLMEngine:
         self._workspaces: Dict[Tuple[int, int], object] = {}
         self.stats = {"prefill_tokens": 0, "prefill_s": 0.0, "decode_steps": 0, "decode_tokens": 0,
                       "decode_s": 0.0, "generate_calls": 0, "graph_captures": 0, "peak_active": 0,
-                      "filtered_steps": 0}
+                      "filtered_steps": 0, "penalised_steps": 0}
 
     # ------------------------------------------------------------------ helpers
     def _bucket(self, n: int) -> int:
@@ -452,7 +482,13 @@ class LLMEngine:
     # ------------------------------------------------------------------ decode
     def _sample(self, logits: torch.Tensor, st_view) -> None:
         """``st_view.filtered``: some row has a top-k / top-p filter.  Such a batch samples from whole rows
-        (gathered on a vocab-parallel engine) with the single-GPU filtered sampler, the same on every rank."""
+        (gathered on a vocab-parallel engine) with the single-GPU filtered sampler, the same on every rank.
+        ``st_view.penalised``: some row has a repetition / frequency / presence penalty; the logits of the
+        tokens it generated are rewritten first -- whole rows, or on the vocab-parallel path this rank's
+        shard (every rank holds the same out_tokens)."""
+        if st_view.penalised:
+            shard = self.model.tp_sampling and not st_view.filtered
+            ops.penalize(logits, st_view, self.model.vocab_offset if shard else 0)
         if st_view.filtered:
             ops.sample(logits, st_view, filtered=True)
         elif self.model.tp_sampling:  # local vocab shard + cross-rank max of the 8-byte Gumbel keys
@@ -460,18 +496,21 @@ class LLMEngine:
         else:
             ops.sample(logits, st_view)
 
-    def _decode_once(self, B: int, filtered: bool = False) -> None:
+    def _decode_once(self, B: int, filtered: bool = False, penalised: bool = False) -> None:
         st = self.state
         logits = self.model.decode(st.next_ids[:B], st.positions[:B], st.seq_idx[:B], st.block_tables[:B],
                                    self.kv.k, self.kv.v, workspace=self._workspace(B),
                                    gather=filtered or not self.model.tp_sampling)
         v = st.view(0, B)
         v.filtered = filtered
+        v.penalised = penalised
         self._sample(logits, v)
 
-    def _decode_steps(self, B: int, steps: int, filtered: bool = False) -> None:
+    def _decode_steps(self, B: int, steps: int, filtered: bool = False, penalised: bool = False) -> None:
         if filtered:
             self.stats["filtered_steps"] += steps
+        if penalised:
+            self.stats["penalised_steps"] += steps
         if self._fault_delay is not None and int(self._fault_delay[0]) == self.model.tp_rank \
                 and self.model.custom_ar is not None:
             delay, self._fault_delay = self._fault_delay[1], None  # once
@@ -481,17 +520,20 @@ class LLMEngine:
             # a filtered step of a vocab-parallel engine gathers the logits on RCCL, which stays outside
             # any capture: it runs eagerly
             for _ in range(steps):
-                self._decode_once(B, filtered)
+                self._decode_once(B, filtered, penalised)
             return
-        g = self._graphs.get(self._graph_key(B, filtered))
+        g = self._graphs.get(self._graph_key(B, filtered, penalised))
         if g is None:
-            g = self._capture(B, filtered)
+            g = self._capture(B, filtered, penalised)
         for _ in range(steps):
             g.replay()
 
-    def _graph_key(self, B: int, filtered: bool) -> tuple:
-        """Key of a decode graph: (bucket, context class), and (bucket, context class, True) for the graph
-        whose sampler filters (captured on first use; ``capture_graphs`` captures the unfiltered ones)."""
+    def _graph_key(self, B: int, filtered: bool, penalised: bool = False) -> tuple:
+        """Key of a decode graph: (bucket, context class), (bucket, context class, True) for the graph
+        whose sampler filters, and (bucket, context class, filtered, "pen") for the graphs that penalise
+        first (all but the plain ones captured on first use; ``capture_graphs`` captures the plain ones)."""
+        if penalised:
+            return (B, self._ctx_cls, filtered, "pen")
         return (B, self._ctx_cls, True) if filtered else (B, self._ctx_cls)
 
     def capture_graphs(self, max_batch: Optional[int] = None) -> int:
@@ -518,7 +560,7 @@ class LLMEngine:
         self._sync()
         return n
 
-    def _capture(self, B: int, filtered: bool = False):
+    def _capture(self, B: int, filtered: bool = False, penalised: bool = False):
         # snapshot state rows the warm-up step will advance, run it eagerly once (lazy kernel-library
         # load, workspace and split-K ticket allocation), restore, then capture.
         st = self.state
@@ -526,17 +568,17 @@ class LLMEngine:
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
-            self._decode_once(B, filtered)  # (a filtered warm-up also allocates the filter workspace)
+            self._decode_once(B, filtered, penalised)  # (a filtered warm-up also allocates the filter workspace)
         torch.cuda.current_stream(self.device).wait_stream(s)
         for f, t in snap.items():
             getattr(st, f)[:B].copy_(t)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._decode_once(B, filtered)
+            self._decode_once(B, filtered, penalised)
         # capture does not execute; restore anyway in case the backend ran the work
         for f, t in snap.items():
             getattr(st, f)[:B].copy_(t)
-        self._graphs[self._graph_key(B, filtered)] = g
+        self._graphs[self._graph_key(B, filtered, penalised)] = g
         self.stats["graph_captures"] += 1
         return g
 
@@ -699,7 +741,7 @@ class LLMEngine:
                 t0 = time.perf_counter()
                 if t_window_end is not None:  # host work + prefill between two windows of running rows
                     self.stats["max_window_gap_s"] = max(self.stats.get("max_window_gap_s", 0.0), t0 - t_window_end)
-                self._decode_steps(B, steps, _any_filtered(active))
+                self._decode_steps(B, steps, _any_filtered(active), _any_penalised(active))
                 self._sync()
                 t_window_end = time.perf_counter()
                 self.stats["decode_s"] += t_window_end - t0
@@ -794,6 +836,7 @@ class LLMEngine:
             st.seeds[s.slot] = int(s.params.seed)
             st.top_k[s.slot] = min(int(s.params.top_k), _I32_MAX)
             st.top_p[s.slot] = float(s.params.top_p)
+            self._set_penalties(s.slot, s.params)
             st.result[s.slot] = 0
             if s.imported is not None:  # no forward pass: KV + first token come from elsewhere
                 self._install(s)
@@ -846,6 +889,12 @@ class LLMEngine:
             prefilling.append(s)
             self.stats["interleaved_prefills"] = self.stats.get("interleaved_prefills", 0) + 1
 
+    def _set_penalties(self, slot: int, params: SamplingParams) -> None:
+        st = self.state
+        st.rep_pen[slot] = float(params.repetition_penalty)
+        st.freq_pen[slot] = float(params.frequency_penalty)
+        st.pres_pen[slot] = float(params.presence_penalty)
+
     def _setup_slot(self, s: _Seq, row: torch.Tensor) -> None:
         """Decode-state row of ``s`` at ``s.slot``: its pages, budget and sampling parameters."""
         st = self.state
@@ -857,6 +906,7 @@ class LLMEngine:
         st.seeds[s.slot] = int(s.params.seed)
         st.top_k[s.slot] = min(int(s.params.top_k), _I32_MAX)
         st.top_p[s.slot] = float(s.params.top_p)
+        self._set_penalties(s.slot, s.params)
         st.result[s.slot] = 0
 
     def _interleaved_pass(self, prefilling: List[_Seq], active: List[_Seq], max_parts: Optional[int] = None) -> None:
@@ -1045,6 +1095,7 @@ class LLMEngine:
             st.max_new[0], st.gen_count[0], st.done[0], st.result[0] = 1, 0, 0, 0
             st.temps[0], st.seeds[0] = float(params.temperature), int(params.seed)
             st.top_k[0], st.top_p[0] = min(int(params.top_k), _I32_MAX), float(params.top_p)
+            self._set_penalties(0, params)
             slices = self.cp_slices(n, world)
             mine = [(b, e) for b, e in slices[rank] if e > b]
             if len(mine) != len(slices[rank]):  # n >= 2 world: every zigzag chunk holds a token

@@ -53,7 +53,7 @@ from typing import Any, Dict, List, Optional, Sequence
 
 from ..config import LLMConfig
 from ..parallel import dist as pdist
-from ..pipeline.providers import GenRequest, GenResult, Provider, request_filters
+from ..pipeline.providers import GenRequest, GenResult, Provider, request_filters, request_penalties
 from .chat import render_chat, render_messages
 from .tokenizer import get_tokenizer
 
@@ -70,10 +70,13 @@ def _req_seed(base: int, req: GenRequest) -> int:
 
 def sampling_params(req: GenRequest, base_seed: int, config=None):
     """The engine's SamplingParams of one request: its budget and temperature, the seed derived from
-    its text, and its top-k / top-p filters (the request's own, else $TOP_K / $TOP_P of ``config``)."""
+    its text, its top-k / top-p filters (the request's own, else $TOP_K / $TOP_P of ``config``) and its
+    frequency / presence / repetition penalties (likewise)."""
     from .engine import SamplingParams
     top_k, top_p = request_filters(req, config)
-    return SamplingParams(req.max_tokens, req.temperature, _req_seed(base_seed, req), top_k=top_k, top_p=top_p)
+    freq, pres, rep = request_penalties(req, config)
+    return SamplingParams(req.max_tokens, req.temperature, _req_seed(base_seed, req), top_k=top_k, top_p=top_p,
+                          frequency_penalty=freq, presence_penalty=pres, repetition_penalty=rep)
 
 
 def parse_parallel(spec: str, world: int) -> Dict[str, int]:

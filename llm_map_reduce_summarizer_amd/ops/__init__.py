@@ -233,6 +233,19 @@ def sample(logits, st, filtered=False):
     reference.sample_finish(toks, st)
 
 
+def penalize(logits, st, tok_offset=0):
+    """Repetition / frequency / presence penalties of decode state ``st`` (``rep_pen`` / ``freq_pen`` /
+    ``pres_pen`` rows) applied in place to the bf16 rows ``logits``, before they are sampled:
+    reference.apply_penalties over the tokens each row has generated so far.  ``logits`` may be a
+    vocabulary shard whose first column is token ``tok_offset``."""
+    if _use_hip(logits):
+        from . import hip
+        return hip.penalize(logits, st, tok_offset)
+    n = logits.shape[0]
+    return reference.apply_penalties(logits, st.out_tokens[:n], st.gen_count[:n], st.rep_pen[:n], st.freq_pen[:n],
+                                     st.pres_pen[:n], st.done[:n], tok_offset)
+
+
 def sample_tp(logits, st, tok_offset, max_reduce):
     """Vocab-parallel sampling over this rank's logits shard (GPU only; see hip.sample_tp)."""
     from . import hip

@@ -58,6 +58,8 @@ _SIGS = {
                    _c_int, _vp],
     "mrsum_sample": [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _vp, _vp,
                      _vp],
+    "mrsum_penalize": [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mrsum_penalize_scan": [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp],
     "mrsum_sample_thresh": [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mrsum_sample_filtered": [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                               _vp, _vp, _c_int, _vp, _vp, _vp],
@@ -650,6 +652,42 @@ def sample(logits: torch.Tensor, st, filtered: bool = False) -> None:
                                _p(st.result), _p(st.next_ids), _p(st.positions), _p(st.gen_count), _p(st.max_new),
                                _p(st.out_tokens), st.out_tokens.stride(0), _p(st.done), _p(st.eos),
                                _stream()), "sample")
+
+
+PENALTY_MAX_TOKENS = 4096  # sampler.hip PEN_CAP: generated tokens per row the penalize kernel's LDS table holds
+
+
+def _penalty_fields_ok(st, B: int) -> None:
+    _req(all(hasattr(st, f) for f in ("rep_pen", "freq_pen", "pres_pen")),
+         "penalize: the state needs rep_pen / freq_pen / pres_pen rows")
+    for t in (st.rep_pen, st.freq_pen, st.pres_pen):
+        _req(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= B,
+             "penalize: rep_pen / freq_pen / pres_pen must be contiguous float32 device rows of the batch")
+    _req(st.gen_count.numel() >= B and st.done.numel() >= B and st.out_tokens.shape[0] >= B,
+         "penalize: state smaller than batch")
+    _i32(st.gen_count, st.done)
+    _req(st.out_tokens.is_cuda and st.out_tokens.dtype == torch.int32 and st.out_tokens.dim() == 2
+         and st.out_tokens.stride(1) == 1, "penalize: out_tokens must be int32 device rows")
+    _req(st.out_tokens.shape[1] <= PENALTY_MAX_TOKENS,
+         "penalize: out_tokens rows of %d tokens exceed the kernel's %d" % (st.out_tokens.shape[1], PENALTY_MAX_TOKENS))
+
+
+def penalize(logits: torch.Tensor, st, tok_offset: int = 0, form: str = "table") -> torch.Tensor:
+    """Repetition / frequency / presence penalties in place on ``logits`` [B, V] (reference.apply_penalties):
+    row b's generated tokens ``st.out_tokens[b, :st.gen_count[b]]`` that fall into the columns' token range
+    [tok_offset, tok_offset + V) are rewritten; neutral, empty and done rows are left alone.  One launch,
+    no workspace, capturable.  ``form`` "scan" runs the ownership-scan variant of the kernel (measurement)."""
+    _bf16_cuda(logits)
+    _req(logits.dim() == 2 and logits.stride(1) == 1, "penalize: expected 2-D row-major logits")
+    B, V = logits.shape
+    _req(tok_offset >= 0, "penalize: negative tok_offset")
+    _req(form in ("table", "scan"), "penalize: unknown form %r" % (form,))
+    _penalty_fields_ok(st, B)
+    name = "mrsum_penalize" if form == "table" else "mrsum_penalize_scan"
+    _check(_fn(name)(_p(logits), logits.stride(0), B, V, int(tok_offset), _p(st.out_tokens), st.out_tokens.stride(0),
+                     _p(st.gen_count), _p(st.done), _p(st.rep_pen), _p(st.freq_pen), _p(st.pres_pen), _stream()),
+           "penalize")
+    return logits
 
 
 def sample_tp(logits: torch.Tensor, st, tok_offset: int, max_reduce) -> None:

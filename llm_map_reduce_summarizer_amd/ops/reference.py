@@ -422,6 +422,42 @@ def nucleus_threshold(logits: torch.Tensor, temps, top_k, top_p) -> torch.Tensor
     return out
 
 
+def apply_penalties(logits: torch.Tensor, out_tokens, gen_count, rep, freq, pres, done=None,
+                    tok_offset: int = 0) -> torch.Tensor:
+    """Repetition / frequency / presence penalties, in place on the bf16 rows ``logits`` [B, V] (returned).
+
+    For row b let c(t) be the number of times token t occurs in ``out_tokens[b, :gen_count[b]]`` -- the
+    GENERATED tokens only, never the prompt.  Every t with c(t) > 0 whose column t - ``tok_offset`` lies in
+    [0, V) is rewritten, each step one individually rounded fp32 operation, in vLLM's order:
+
+        x = float32(logit);  x = x / rep if x > 0 else x * rep  (when rep != 1);
+        x = x - fl32(freq * c);  x = x - pres;  logit = bf16(x)  (round to nearest even)
+
+    Every other entry keeps its bits.  A row with rep == 1, freq == 0 and pres == 0, with gen_count == 0 or
+    with ``done`` set is untouched.  ``tok_offset`` / V describe a vocabulary shard: penalising the shards
+    of a row one by one equals penalising the whole row.  sampler.hip's penalize kernel matches it bit for
+    bit."""
+    B, V = logits.shape
+    for b in range(B):
+        r = torch.tensor(float(rep[b]), dtype=torch.float32)
+        f = torch.tensor(float(freq[b]), dtype=torch.float32)
+        p = torch.tensor(float(pres[b]), dtype=torch.float32)
+        g = int(gen_count[b])
+        if (float(r) == 1.0 and float(f) == 0.0 and float(p) == 0.0) or g <= 0 or (done is not None and int(done[b])):
+            continue
+        toks, counts = torch.unique(out_tokens[b, :g].to(torch.int64).cpu(), return_counts=True)
+        cols = toks - int(tok_offset)
+        keep = (cols >= 0) & (cols < V)
+        cols, counts = cols[keep].to(logits.device), counts[keep].to(logits.device)
+        x = logits[b, cols].to(torch.float32)
+        if float(r) != 1.0:
+            x = torch.where(x > 0, x / r, x * r)
+        x = x - f * counts.to(torch.float32)
+        x = x - p
+        logits[b, cols] = x.to(logits.dtype)
+    return logits
+
+
 def sample_tokens(logits: torch.Tensor, temps: torch.Tensor, seeds: torch.Tensor,
                   positions: torch.Tensor, thresh: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Gumbel-max sampling (argmax when temperature <= 0); ties -> lowest id.  ``thresh`` (fp32 [B],

@@ -45,6 +45,11 @@ class GenRequest:
     # sampling filters; None = the configured default ($TOP_K / $TOP_P: 0 / 1.0 = off)
     top_k: Optional[int] = None
     top_p: Optional[float] = None
+    # penalties on the tokens generated so far; None = the configured default ($FREQUENCY_PENALTY /
+    # $PRESENCE_PENALTY / $REPETITION_PENALTY: 0 / 0 / 1 = off)
+    frequency_penalty: Optional[float] = None
+    presence_penalty: Optional[float] = None
+    repetition_penalty: Optional[float] = None
 
 
 def request_filters(req: GenRequest, config: Optional[LLMConfig]) -> Tuple[int, float]:
@@ -52,6 +57,15 @@ def request_filters(req: GenRequest, config: Optional[LLMConfig]) -> Tuple[int, 
     k = req.top_k if req.top_k is not None else getattr(config, "TOP_K", 0)
     p = req.top_p if req.top_p is not None else getattr(config, "TOP_P", 1.0)
     return int(k), float(p)
+
+
+def request_penalties(req: GenRequest, config: Optional[LLMConfig]) -> Tuple[float, float, float]:
+    """(frequency_penalty, presence_penalty, repetition_penalty) of a request: its own values, else the
+    configured defaults (0 / 0 / 1 = off)."""
+    f = req.frequency_penalty if req.frequency_penalty is not None else getattr(config, "FREQUENCY_PENALTY", 0.0)
+    p = req.presence_penalty if req.presence_penalty is not None else getattr(config, "PRESENCE_PENALTY", 0.0)
+    r = req.repetition_penalty if req.repetition_penalty is not None else getattr(config, "REPETITION_PENALTY", 1.0)
+    return float(f), float(p), float(r)
 
 
 @dataclass
@@ -196,6 +210,11 @@ class OpenAIProvider(_HTTPProvider):
         _k, top_p = request_filters(req, self.config)  # the OpenAI API has no top_k
         if top_p < 1.0:
             body["top_p"] = top_p
+        freq, pres, _rep = request_penalties(req, self.config)  # the OpenAI API has no repetition_penalty
+        if freq != 0.0:
+            body["frequency_penalty"] = freq
+        if pres != 0.0:
+            body["presence_penalty"] = pres
         data = await self._post(headers, body)
         usage = data.get("usage", {})
         pt, ct = usage.get("prompt_tokens", 0), usage.get("completion_tokens", 0)
@@ -223,6 +242,7 @@ class AnthropicProvider(_HTTPProvider):
             body["top_p"] = top_p
         if top_k > 0:
             body["top_k"] = top_k
+        # (the Anthropic API has no frequency / presence / repetition penalty: none is sent)
         data = await self._post(headers, body)
         text = data["content"][0]["text"]
         usage = data.get("usage") or {}

@@ -15,7 +15,9 @@ Endpoints: ``POST /v1/chat/completions``, ``POST /v1/messages``, ``GET /v1/model
 on a single-process engine, the whole completion as one event under torchrun; Anthropic streaming gets the
 message as one event.  ``top_p`` (both endpoints) and ``top_k`` (``/v1/messages``; on the chat endpoint as
 the common extension) restrict the sample on the GPU (sampler.hip's filter kernels); a value out of range
-or not a number is a 400.  Stop sequences and n > 1 are not supported (400).
+or not a number is a 400.  ``frequency_penalty`` / ``presence_penalty`` (numbers in [-2, 2], the OpenAI
+range) and ``repetition_penalty`` (the common extension, a number in (0, 2]) act on the tokens generated so
+far (sampler.hip's penalize kernel), on both endpoints; anything else is a 400.  Stop sequences and n > 1 are not supported (400).
 
 Batching: HTTP handlers only enqueue; one engine thread owns the engine.  Single process
 (``ContinuousBatcher``): the first requests start a generate and every request that arrives while it runs
@@ -99,6 +101,22 @@ def _filters(body: Dict[str, Any]) -> Dict[str, Any]:
     return out
 
 
+def _penalties(body: Dict[str, Any]) -> Dict[str, Any]:
+    """``frequency_penalty`` / ``presence_penalty`` / ``repetition_penalty`` of a request body as GenRequest
+    fields (absent or null: the server's default)."""
+    out: Dict[str, Any] = {}
+    for name, lo, hi, rng in (("frequency_penalty", -2.0, 2.0, "[-2, 2]"), ("presence_penalty", -2.0, 2.0, "[-2, 2]"),
+                              ("repetition_penalty", 0.0, 2.0, "(0, 2]")):
+        x = body.get(name)
+        if x is None:
+            continue
+        ok = not isinstance(x, bool) and isinstance(x, (int, float)) and lo <= float(x) <= hi  # NaN fails
+        if not ok or (name == "repetition_penalty" and float(x) <= 0.0):
+            raise BadRequest("%s must be a number in %s" % (name, rng))
+        out[name] = float(x)
+    return out
+
+
 def openai_request(body: Dict[str, Any], default_temp: float = 1.0) -> GenRequest:
     """GenRequest of an OpenAI ``/v1/chat/completions`` body.  A [system?, user] chat keeps the
     reference's request shape (same prompt rendering and seed as the in-process provider)."""
@@ -114,7 +132,7 @@ def openai_request(body: Dict[str, Any], default_temp: float = 1.0) -> GenReques
             raise BadRequest("unsupported message role %r" % role)
         turns.append({"role": role, "content": _text(m.get("content", ""))})
     max_tokens, temp = _common(body, default_temp)
-    filters = _filters(body)
+    filters = {**_filters(body), **_penalties(body)}
     roles = [t["role"] for t in turns]
     if roles in (["user"], ["system", "user"]):
         return GenRequest(user=turns[-1]["content"], system=turns[0]["content"] if len(turns) == 2 else None,
@@ -137,7 +155,7 @@ def anthropic_request(body: Dict[str, Any], default_temp: float = 1.0) -> GenReq
             raise BadRequest("unsupported message role %r" % role)
         turns.append({"role": role, "content": _text(m.get("content", ""))})
     max_tokens, temp = _common(body, default_temp)
-    filters = _filters(body)
+    filters = {**_filters(body), **_penalties(body)}
     if [t["role"] for t in turns[-1:]] != ["user"]:
         raise BadRequest("the last message must be from the user")
     if len(msgs) == 1:

@@ -10,6 +10,13 @@ launch), ``all`` (every row top_k=40 top_p=0.9), ``one`` (row 0 filtered, the ot
 filter kernels at once), ``thresh`` (the two filter kernels alone, every row filtered).
 
     python tools/bench_sampler.py --bs 1,10,39 > profiles/sampler_filter.jsonl
+
+``--penalties``: the cost of the penalize launch (ops.hip.penalize, which a penalised decode step runs
+before the sampler) instead, timed the same way, for every row penalised with ``gen_count`` generated
+tokens (half as many distinct ids), in both forms of the kernel's token reduction -- ``table`` (the LDS
+open-addressing table the engine runs) and ``scan`` (the ownership scan).
+
+    python tools/bench_sampler.py --penalties --bs 1,10,39 > profiles/sampler_penalties.jsonl
 """
 import argparse
 import json
@@ -25,6 +32,8 @@ ap.add_argument("--iters", type=int, default=200)
 ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--temperature", type=float, default=0.3)
 ap.add_argument("--scale", type=float, default=3.0, help="std of the random logits")
+ap.add_argument("--penalties", action="store_true", help="time the penalize launch instead of the filter")
+ap.add_argument("--gen-counts", default="1,256,2048", help="--penalties: generated tokens per row")
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.tree))
 
@@ -80,6 +89,28 @@ for B in (int(b) for b in args.bs.split(",")):
 
     def rewrite(i):
         logits.copy_(srcs[i % NSRC])
+
+    if args.penalties:
+        for gc in (int(x) for x in args.gen_counts.split(",")):
+            st = State(B, max(gc, 2048), [0] * B, [1.0] * B)
+            pool = torch.randint(0, args.vocab, (B, max(1, gc // 2)), generator=g)
+            st.out_tokens[:, :gc] = torch.gather(pool, 1, torch.randint(0, pool.shape[1], (B, gc), generator=g)).to(dev)
+            st.gen_count.fill_(gc)
+            st.rep_pen = torch.full((B,), 1.2, dtype=torch.float32, device=dev)
+            st.freq_pen = torch.full((B,), 0.5, dtype=torch.float32, device=dev)
+            st.pres_pen = torch.full((B,), 0.5, dtype=torch.float32, device=dev)
+            rec = {"B": B, "V": args.vocab, "gen_count": gc, "iters": args.iters, "repeats": args.repeats}
+            for form in ("table", "scan"):
+                def step(i, st=st, form=form):
+                    rewrite(i)
+                    hip.penalize(logits, st, form=form)
+
+                timed(step, args.iters)
+                d = [timed(step, args.iters) - timed(rewrite, args.iters) for _ in range(args.repeats)]
+                rec["penalize_%s_us" % form] = round(statistics.median(d), 2)
+                rec["penalize_%s_us_min_max" % form] = [round(min(d), 2), round(max(d), 2)]
+            print(json.dumps(rec), flush=True)
+        continue
 
     res = {}
     for mode, (ks, ps) in modes.items():
