@@ -79,6 +79,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="override $REPETITION_PENALTY: divides the positive / multiplies the negative logits "
                         "of the tokens the sequence has GENERATED (the prompt is not counted, unlike HF / "
                         "vLLM), map and reduce (> 0; 1.0 = off)")
+    g.add_argument("--min-new-tokens", type=int, default=None,
+                   help="override $MIN_NEW_TOKENS: no end-of-turn / stop id can be sampled before this many "
+                        "tokens are generated, map and reduce (0 = off)")
+    g.add_argument("--logit-bias", default=None, metavar="ID:BIAS,ID:BIAS",
+                   help="override $LOGIT_BIAS: added to the logits of these token ids of the local tokenizer, "
+                        "map and reduce; BIAS in [-100, 100], or 'ban' to forbid the token (empty = off)")
     g.add_argument("--fault-inject", type=float, default=0.0, help="mock provider: failure probability")
     g.add_argument("--profile", default=None, metavar="DIR",
                    help="torch.profiler trace of the run: DIR/trace_rank{r}.json + top-kernel table")
@@ -157,6 +163,17 @@ def config_from_args(args: argparse.Namespace):
     if not all(math.isfinite(x) for x in pens) or not cfg.REPETITION_PENALTY > 0:
         raise SystemExit("frequency / presence penalty must be finite and repetition penalty > 0, got %r / %r / %r"
                          % pens)
+    if getattr(args, "min_new_tokens", None) is not None:
+        cfg.MIN_NEW_TOKENS = args.min_new_tokens
+    if getattr(args, "logit_bias", None) is not None:
+        cfg.LOGIT_BIAS = args.logit_bias
+    if cfg.MIN_NEW_TOKENS < 0:
+        raise SystemExit("min-new-tokens must be >= 0, got %r" % (cfg.MIN_NEW_TOKENS,))
+    try:
+        from .config import parse_logit_bias
+        parse_logit_bias(cfg.LOGIT_BIAS)
+    except ValueError as e:
+        raise SystemExit(str(e))
     return cfg
 
 

@@ -49,6 +49,31 @@ def _env(key: str, default: str) -> str:
     return os.environ.get(key, default)
 
 
+def parse_logit_bias(spec: str):
+    """``"ID:BIAS,ID:BIAS"`` ($LOGIT_BIAS / --logit-bias) as [(token id, bias)]; a BIAS written ``ban`` is
+    -inf.  Raises ValueError for anything else, a repeated id and a bias outside [-100, 100] included."""
+    out = []
+    for part in (x.strip() for x in spec.split(",")):
+        if not part:
+            continue
+        tok, sep, bias = part.partition(":")
+        try:
+            if not sep:
+                raise ValueError
+            t = int(tok.strip())
+            x = float("-inf") if bias.strip().lower() == "ban" else float(bias)
+        except ValueError:
+            raise ValueError("logit bias entry %r is not ID:BIAS (BIAS a number or 'ban')" % part) from None
+        if t < 0 or not (x == float("-inf") or -100.0 <= x <= 100.0):  # (NaN fails the range)
+            raise ValueError("logit bias entry %r needs an id >= 0 and a bias in [-100, 100] or 'ban'" % part)
+        out.append((t, x))
+    if len({t for t, _ in out}) != len(out):
+        raise ValueError("logit bias %r names a token twice" % spec)
+    if len(out) > 300:
+        raise ValueError("logit bias holds %d entries, at most 300 are allowed" % len(out))
+    return out
+
+
 class LLMConfig:
     """Provider + generation settings.  Class attributes = values at import time."""
 
@@ -68,6 +93,9 @@ class LLMConfig:
         # penalties on the tokens a sequence has generated, map and reduce (0 / 0 / 1 = off)
         "FREQUENCY_PENALTY": ("0.0", float), "PRESENCE_PENALTY": ("0.0", float),
         "REPETITION_PENALTY": ("1.0", float),
+        # constraints, map and reduce: fewest tokens before a stop id can be sampled (0 = off) and a logit bias
+        # "ID:BIAS,ID:BIAS" over the local tokenizer's ids, BIAS in [-100, 100] or "ban" (empty = off)
+        "MIN_NEW_TOKENS": ("0", int), "LOGIT_BIAS": ("", str),
         # hosted-provider endpoints (new): point the adapters at any compatible server
         "OPENAI_BASE_URL": ("https://api.openai.com/v1", str),
         "ANTHROPIC_BASE_URL": ("https://api.anthropic.com/v1", str),

@@ -342,6 +342,54 @@ __global__ __launch_bounds__(PEN_THREADS) void penalize_kernel(bf16* __restrict_
     }
 }
 
+// ------------------------------------------------------------------ logit bias / minimum length / row stop ids
+// constrain: one workgroup per row rewrites, in place and before the penalties, the filter and the sampler
+//          run, the logits a request constrains (ops/reference.py apply_constraints is the definition):
+//          entry i < bias_n[b] of the row's (bias_tok, bias_val) list -- one thread per entry, the tokens of
+//          a row are distinct -- becomes bf16(float(x) + bias), one rounded fp32 add, or -inf when the bias is
+//          -inf (a ban: stored, not added, so a +inf logit is banned too and no NaN appears; a NaN logit
+//          stays a NaN).  Then, after a barrier (suppression wins over a bias on the same token), a row with
+//          gen_count[b] < min_new[b] gets -inf at every armed stop id: the engine's EOS_SLOTS ids and the
+//          row's STOP_SLOTS own ones, both read from device memory at EVERY launch (-1 = unused slot), so a
+//          captured graph follows generate(ignore_eos=True) at replay.  Columns are shard-local (tok_offset /
+//          V, as in penalize).  No global atomics, no workspace; a neutral or done row costs one early-exit
+//          workgroup.
+constexpr int CON_THREADS = 320;  // 5 waves: one pass over the 300 entries a row may hold (OpenAI's limit)
+constexpr int STOP_SLOTS = 4;     // engine DecodeState.stop_ids: 4 device ints per row, -1 = unused
+
+__global__ __launch_bounds__(CON_THREADS) void constrain_kernel(bf16* __restrict__ logits, int ld, int V,
+                                                                int tok_offset, const int* __restrict__ bias_tok,
+                                                                const float* __restrict__ bias_val, int bias_stride,
+                                                                const int* __restrict__ bias_n,
+                                                                const int* __restrict__ gen_count,
+                                                                const int* __restrict__ min_new,
+                                                                const int* __restrict__ stop_ids,
+                                                                const int* __restrict__ eos,
+                                                                const int* __restrict__ done) {
+    const int b = blockIdx.x;
+    const int n = min(bias_n[b], bias_stride);
+    const bool suppress = gen_count[b] < min_new[b];
+    if ((n <= 0 && !suppress) || (done != nullptr && done[b])) return;  // block-uniform
+    bf16* row = logits + (size_t)b * ld;
+    unsigned short* rbits = reinterpret_cast<unsigned short*>(row);
+    for (int i = threadIdx.x; i < n; i += CON_THREADS) {
+        const unsigned int col = (unsigned int)bias_tok[(size_t)b * bias_stride + i] - (unsigned int)tok_offset;
+        if (col >= (unsigned int)V) continue;  // another shard's token
+        const float bias = bias_val[(size_t)b * bias_stride + i];
+        const float x = (float)row[col];
+        if (bias != -INFINITY) row[col] = (bf16)(x + bias);
+        else if (x == x) rbits[col] = 0xff80u;  // -inf
+    }
+    if (!suppress) return;  // block-uniform
+    __syncthreads();  // the biased logits are written: a suppressed stop id overwrites its bias
+    if (threadIdx.x < EOS_SLOTS + STOP_SLOTS) {
+        const int t = threadIdx.x < EOS_SLOTS ? eos[threadIdx.x]
+                                              : stop_ids[(size_t)b * STOP_SLOTS + (threadIdx.x - EOS_SLOTS)];
+        const unsigned int col = (unsigned int)t - (unsigned int)tok_offset;
+        if (t >= 0 && col < (unsigned int)V) rbits[col] = 0xff80u;
+    }
+}
+
 template <bool FILTER>
 __global__ __launch_bounds__(256) void sample_kernel(const bf16* __restrict__ logits, int ld, int V, int tok_offset,
                                                      const float* __restrict__ temps,
@@ -400,10 +448,15 @@ __global__ __launch_bounds__(256) void sample_kernel(const bf16* __restrict__ lo
     }
 }
 
-__global__ void sample_finish_kernel(unsigned long long* __restrict__ result, int* __restrict__ next_ids,
-                                     int* __restrict__ positions, int* __restrict__ gen_count,
-                                     const int* __restrict__ max_new, int* __restrict__ out_tokens, int out_stride,
-                                     int* __restrict__ done, const int* __restrict__ eos, int B) {
+// ROW_STOPS: the row's own STOP_SLOTS stop ids (stop_ids[b], -1 = unused) retire it like an EOS id, the
+// token appended as an EOS id is.  ROW_STOPS = false never touches stop_ids: the plain finish, instruction
+// for instruction the kernel it was before the row stops existed.
+template <bool ROW_STOPS>
+__device__ __forceinline__ void finish_row(unsigned long long* __restrict__ result, int* __restrict__ next_ids,
+                                           int* __restrict__ positions, int* __restrict__ gen_count,
+                                           const int* __restrict__ max_new, int* __restrict__ out_tokens,
+                                           int out_stride, int* __restrict__ done, const int* __restrict__ eos,
+                                           const int* __restrict__ stop_ids, int B) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const unsigned long long r = result[b];
@@ -417,8 +470,27 @@ __global__ void sample_finish_kernel(unsigned long long* __restrict__ result, in
     bool stop = g + 1 >= max_new[b];
 #pragma unroll
     for (int i = 0; i < EOS_SLOTS; ++i) stop |= tok == eos[i];  // tok >= 0 never matches a -1 slot
+    if constexpr (ROW_STOPS) {
+        const int4 own = *reinterpret_cast<const int4*>(stop_ids + (size_t)b * STOP_SLOTS);  // 16-B aligned rows
+        stop |= tok == own.x || tok == own.y || tok == own.z || tok == own.w;
+    }
     if (stop) done[b] = 1;
     else positions[b] += 1;
+}
+
+__global__ void sample_finish_kernel(unsigned long long* __restrict__ result, int* __restrict__ next_ids,
+                                     int* __restrict__ positions, int* __restrict__ gen_count,
+                                     const int* __restrict__ max_new, int* __restrict__ out_tokens, int out_stride,
+                                     int* __restrict__ done, const int* __restrict__ eos, int B) {
+    finish_row<false>(result, next_ids, positions, gen_count, max_new, out_tokens, out_stride, done, eos, nullptr, B);
+}
+
+__global__ void sample_finish_stops_kernel(unsigned long long* __restrict__ result, int* __restrict__ next_ids,
+                                           int* __restrict__ positions, int* __restrict__ gen_count,
+                                           const int* __restrict__ max_new, int* __restrict__ out_tokens,
+                                           int out_stride, int* __restrict__ done, const int* __restrict__ eos,
+                                           const int* __restrict__ stop_ids, int B) {
+    finish_row<true>(result, next_ids, positions, gen_count, max_new, out_tokens, out_stride, done, eos, stop_ids, B);
 }
 
 static int launch_keys(const void* logits, int ld, int B, int V, int tok_offset, const float* temps,
@@ -517,5 +589,49 @@ MRSUM_API int mrsum_penalize_scan(void* logits, int ld, int B, int V, int tok_of
     if (B <= 0) return 0;
     penalize_kernel<false><<<B, PEN_THREADS, 0, s>>>((bf16*)logits, ld, V, tok_offset, out_tokens, out_stride,
                                                      gen_count, done, rep, freq, pres);
+    return (int)hipGetLastError();
+}
+
+// Logit bias, minimum length (armed stop ids at -inf while gen_count < min_new) on the logits rows, in place,
+// ahead of the penalties and of any sampler launch on stream s (capturable).  bias_tok / bias_val: rows of
+// bias_stride entries, the first bias_n[b] of row b valid; stop_ids: B x 4 ints; eos: the engine's 4 ints.
+// V / tok_offset describe a vocabulary shard as in mrsum_penalize.  done may be null.
+MRSUM_API int mrsum_constrain(void* logits, int ld, int B, int V, int tok_offset, const int* bias_tok,
+                              const float* bias_val, int bias_stride, const int* bias_n, const int* gen_count,
+                              const int* min_new, const int* stop_ids, const int* eos, const int* done,
+                              hipStream_t s) {
+    if (B <= 0) return 0;
+    constrain_kernel<<<B, CON_THREADS, 0, s>>>((bf16*)logits, ld, V, tok_offset, bias_tok, bias_val, bias_stride,
+                                               bias_n, gen_count, min_new, stop_ids, eos, done);
+    return (int)hipGetLastError();
+}
+
+// mrsum_sample_finish that also retires a row whose new token is one of its own stop ids (stop_ids: B x 4
+// ints, 16-byte aligned, -1 = unused slot).
+MRSUM_API int mrsum_sample_finish_stops(void* result, int* next_ids, int* positions_rw, int* gen_count,
+                                        const int* max_new, int* out_tokens, int out_stride, int* done,
+                                        const int* eos, const int* stop_ids, int B, hipStream_t s) {
+    if (B <= 0) return 0;
+    sample_finish_stops_kernel<<<ceil_div(B, 64), 64, 0, s>>>((unsigned long long*)result, next_ids, positions_rw,
+                                                              gen_count, max_new, out_tokens, out_stride, done, eos,
+                                                              stop_ids, B);
+    return (int)hipGetLastError();
+}
+
+// The first two stages of mrsum_sample_filtered -- thresholds, then the Gumbel-max keys over the kept tokens
+// of whole rows folded into result[b] -- without the finish, so that a constrained step ends in
+// mrsum_sample_finish_stops.
+MRSUM_API int mrsum_sample_keys_filtered(const void* logits, int ld, int B, int V, const float* temps,
+                                         const long long* seeds, const int* positions, const int* top_k,
+                                         const float* top_p, const int* done, float* thresh, void* hist,
+                                         void* result, hipStream_t s) {
+    if (B <= 0) return 0;
+    int e = mrsum_sample_thresh(logits, ld, B, V, temps, top_k, top_p, done, thresh, hist, s);
+    if (e) return e;
+    const int nseg = 32;
+    int seg_len = ceil_div(V, nseg);
+    seg_len = (seg_len + 7) & ~7;
+    sample_kernel<true><<<dim3(nseg, B), 256, 0, s>>>((const bf16*)logits, ld, V, 0, temps, seeds, positions,
+                                                      (unsigned long long*)result, seg_len, thresh);
     return (int)hipGetLastError();
 }

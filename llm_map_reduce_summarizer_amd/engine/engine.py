@@ -27,7 +27,7 @@ import os
 import time
 from dataclasses import dataclass, field, replace
 from types import SimpleNamespace
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Mapping, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -42,6 +42,8 @@ log = logging.getLogger("mrsum.engine")
 BUCKETS = (1, 2, 4, 8, 16, 24, 32, 40, 48, 64, 80, 96, 128, 160, 192, 224, 256)
 MAX_WINDOW = 256  # decode steps between host syncs when no row can stop early (LLMEngine._window)
 _I32_MAX = 2 ** 31 - 1  # DecodeState.top_k is int32; any k >= the vocabulary size means "off"
+MAX_LOGIT_BIAS = 300  # logit_bias entries per request (OpenAI's limit; DecodeState.bias_tok row width)
+MAX_STOP_IDS = 4  # stop_token_ids per request (DecodeState.stop_ids row width, sampler.hip STOP_SLOTS)
 
 
 def _always() -> bool:
@@ -58,6 +60,11 @@ def _any_penalised(seqs) -> bool:
     return any(s.params.penalised for s in seqs)
 
 
+def _any_constrained(seqs) -> bool:
+    """Whether any of these sequences carries a logit bias, a minimum length or stop ids of its own."""
+    return any(s.params.constrained for s in seqs)
+
+
 @dataclass
 class SamplingParams:
     max_new_tokens: int = 1000
@@ -71,6 +78,58 @@ class SamplingParams:
     frequency_penalty: float = 0.0
     presence_penalty: float = 0.0
     repetition_penalty: float = 1.0
+    # constraints (ops.reference.apply_constraints), applied before the penalties and the filter, to the
+    # first token too.  logit_bias: {token: bias} or [(token, bias)], at most 300 distinct tokens, a bias a
+    # finite number in [-100, 100] added to the token's logit, or float("-inf"): the token is banned.
+    # min_tokens: no stop id (the engine's EOS ids, stop_token_ids) can be sampled before this many tokens
+    # are out.  stop_token_ids: at most 4 ids that end this request like an EOS id (finish_reason "stop")
+    logit_bias: Union[Mapping[int, float], Sequence[Tuple[int, float]], None] = None
+    min_tokens: int = 0
+    stop_token_ids: Sequence[int] = ()
+
+    @property
+    def constrained(self) -> bool:
+        """Whether these parameters carry a logit bias, a minimum length or stop ids of their own."""
+        return bool(self.logit_bias) or self.min_tokens > 0 or len(self.stop_token_ids) > 0
+
+    def bias_items(self) -> List[Tuple[int, float]]:
+        """``logit_bias`` as a list of (token, bias) pairs."""
+        lb = self.logit_bias
+        if not lb:
+            return []
+        return [(t, x) for t, x in (lb.items() if isinstance(lb, Mapping) else lb)]
+
+    def _validate_constraints(self, vocab: Optional[int]) -> None:
+        def token(t) -> bool:
+            return not isinstance(t, bool) and isinstance(t, int) and 0 <= t and (vocab is None or t < vocab)
+
+        lb = self.logit_bias
+        if lb is not None and not isinstance(lb, (Mapping, list, tuple)):
+            raise ValueError("logit_bias must be a mapping or a sequence of (token, bias), got %r" % (lb,))
+        try:
+            items = self.bias_items()
+        except (TypeError, ValueError):
+            raise ValueError("logit_bias must be a mapping or a sequence of (token, bias), got %r" % (lb,)) from None
+        if len(items) > MAX_LOGIT_BIAS:
+            raise ValueError("logit_bias holds %d entries, at most %d are allowed" % (len(items), MAX_LOGIT_BIAS))
+        for t, x in items:
+            if not token(t):
+                raise ValueError("logit_bias token ids must be integers in [0, vocabulary size), got %r" % (t,))
+            if isinstance(x, bool) or not isinstance(x, (int, float)) or not (x == float("-inf") or -100 <= x <= 100):
+                raise ValueError("a logit bias must be a number in [-100, 100] or -inf (a ban), got %r" % (x,))
+        if len({t for t, _ in items}) != len(items):
+            raise ValueError("logit_bias names a token twice")
+        stops = self.stop_token_ids
+        if isinstance(stops, (str, bytes)) or not isinstance(stops, (list, tuple)) or len(stops) > MAX_STOP_IDS:
+            raise ValueError("stop_token_ids must be a sequence of at most %d token ids, got %r"
+                             % (MAX_STOP_IDS, stops))
+        for t in stops:
+            if not token(t):
+                raise ValueError("stop_token_ids must be integers in [0, vocabulary size), got %r" % (t,))
+        m = self.min_tokens
+        if isinstance(m, bool) or not isinstance(m, int) or not 0 <= m <= self.max_new_tokens:
+            raise ValueError("min_tokens must be an integer in [0, max_new_tokens = %r], got %r"
+                             % (self.max_new_tokens, m))
 
     @property
     def filtered(self) -> bool:
@@ -82,8 +141,10 @@ class SamplingParams:
         """Whether these parameters change the logits of tokens already generated (greedy rows included)."""
         return self.frequency_penalty != 0 or self.presence_penalty != 0 or self.repetition_penalty != 1
 
-    def validate(self) -> None:
+    def validate(self, vocab: Optional[int] = None) -> None:
+        """Raise ValueError for a value out of range; ``vocab``: the vocabulary size token ids must be below."""
         k, p = self.top_k, self.top_p
+        self._validate_constraints(vocab)
         for name in ("frequency_penalty", "presence_penalty", "repetition_penalty"):
             x = getattr(self, name)
             if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x):
@@ -151,6 +212,14 @@ class DecodeState:
         self.rep_pen = torch.ones(max_seqs, dtype=torch.float32, device=device)
         self.freq_pen = torch.zeros(max_seqs, dtype=torch.float32, device=device)
         self.pres_pen = torch.zeros(max_seqs, dtype=torch.float32, device=device)
+        # constraints of every row (ops.reference.apply_constraints): the first bias_n entries of (bias_tok,
+        # bias_val) are its logit bias (-inf = ban), no armed stop id can be sampled while gen_count < min_new,
+        # and the row's own stop ids (-1 = unused slot) retire it like the eos ids below
+        self.bias_tok = torch.zeros(max_seqs, MAX_LOGIT_BIAS, **i32)
+        self.bias_val = torch.zeros(max_seqs, MAX_LOGIT_BIAS, dtype=torch.float32, device=device)
+        self.bias_n = torch.zeros(max_seqs, **i32)
+        self.min_new = torch.zeros(max_seqs, **i32)
+        self.stop_ids = torch.full((max_seqs, MAX_STOP_IDS), -1, **i32)
         self.filter_ws = None
         if self.temps.is_cuda:
             from ..ops.hip import FilterWorkspace
@@ -170,7 +239,8 @@ class DecodeState:
         self.eos_ids = ids
 
     _ROW_FIELDS = ("next_ids", "positions", "block_tables", "gen_count", "max_new", "out_tokens", "done", "result",
-                   "temps", "seeds", "top_k", "top_p", "thresh", "rep_pen", "freq_pen", "pres_pen")
+                   "temps", "seeds", "top_k", "top_p", "thresh", "rep_pen", "freq_pen", "pres_pen",
+                   "bias_tok", "bias_val", "bias_n", "min_new", "stop_ids")
 
     def view(self, start: int, n: int) -> "DecodeState":
         v = object.__new__(DecodeState)
@@ -182,6 +252,7 @@ class DecodeState:
         v.filter_ws = self.filter_ws
         v.filtered = False  # set by the engine on the view of a batch with a top-k / top-p row
         v.penalised = False  # ... and of a batch with a penalised row
+        v.constrained = False  # ... and of a batch with a constrained row (bias / min_new / stop_ids)
         return v
 
     def move_row(self, src: int, dst: int) -> None:
@@ -196,6 +267,8 @@ class DecodeState:
         self.block_tables[i].zero_()
         self.gen_count[i] = 0
         self.rep_pen[i], self.freq_pen[i], self.pres_pen[i] = 1.0, 0.0, 0.0
+        self.bias_n[i], self.min_new[i] = 0, 0
+        self.stop_ids[i].fill_(-1)
 
 
 class _CPExchange:
@@ -341,7 +414,8 @@ class LLMEngine:
         self._workspaces: Dict[Tuple[int, int], object] = {}
         self.stats = {"prefill_tokens": 0, "prefill_s": 0.0, "decode_steps": 0, "decode_tokens": 0,
                       "decode_s": 0.0, "generate_calls": 0, "graph_captures": 0, "peak_active": 0,
-                      "filtered_steps": 0, "penalised_steps": 0}
+                      "filtered_steps": 0, "penalised_steps": 0, "constrained_steps": 0}
+        self._ignore_eos = False  # set for the length of a generate(ignore_eos=True)
 
     # ------------------------------------------------------------------ helpers
     def _bucket(self, n: int) -> int:
@@ -461,6 +535,9 @@ class LLMEngine:
         if filtered:
             self.stats["filtered_steps"] += 1  # the first token is filtered like every other
         v.filtered = filtered
+        v.constrained = _any_constrained(seqs)  # gen_count is 0: the first token is constrained like any other
+        if v.constrained:
+            self.stats["constrained_steps"] += 1
         self._sample(logits, v)
 
     def _gather(self, seqs: Sequence[_Seq]) -> bool:
@@ -485,9 +562,14 @@ class LLMEngine:
         (gathered on a vocab-parallel engine) with the single-GPU filtered sampler, the same on every rank.
         ``st_view.penalised``: some row has a repetition / frequency / presence penalty; the logits of the
         tokens it generated are rewritten first -- whole rows, or on the vocab-parallel path this rank's
-        shard (every rank holds the same out_tokens)."""
+        shard (every rank holds the same out_tokens).
+        ``st_view.constrained``: some row has a logit bias, a minimum length or stop ids of its own; the
+        logits are constrained before anything else, on the same columns as the penalties, and the sampler
+        ends in the finish that honours the rows' stop ids."""
+        shard = self.model.tp_sampling and not st_view.filtered
+        if st_view.constrained:
+            ops.constrain(logits, st_view, self.model.vocab_offset if shard else 0)
         if st_view.penalised:
-            shard = self.model.tp_sampling and not st_view.filtered
             ops.penalize(logits, st_view, self.model.vocab_offset if shard else 0)
         if st_view.filtered:
             ops.sample(logits, st_view, filtered=True)
@@ -496,7 +578,8 @@ class LLMEngine:
         else:
             ops.sample(logits, st_view)
 
-    def _decode_once(self, B: int, filtered: bool = False, penalised: bool = False) -> None:
+    def _decode_once(self, B: int, filtered: bool = False, penalised: bool = False,
+                     constrained: bool = False) -> None:
         st = self.state
         logits = self.model.decode(st.next_ids[:B], st.positions[:B], st.seq_idx[:B], st.block_tables[:B],
                                    self.kv.k, self.kv.v, workspace=self._workspace(B),
@@ -504,13 +587,17 @@ class LLMEngine:
         v = st.view(0, B)
         v.filtered = filtered
         v.penalised = penalised
+        v.constrained = constrained
         self._sample(logits, v)
 
-    def _decode_steps(self, B: int, steps: int, filtered: bool = False, penalised: bool = False) -> None:
+    def _decode_steps(self, B: int, steps: int, filtered: bool = False, penalised: bool = False,
+                      constrained: bool = False) -> None:
         if filtered:
             self.stats["filtered_steps"] += steps
         if penalised:
             self.stats["penalised_steps"] += steps
+        if constrained:
+            self.stats["constrained_steps"] += steps
         if self._fault_delay is not None and int(self._fault_delay[0]) == self.model.tp_rank \
                 and self.model.custom_ar is not None:
             delay, self._fault_delay = self._fault_delay[1], None  # once
@@ -520,18 +607,22 @@ class LLMEngine:
             # a filtered step of a vocab-parallel engine gathers the logits on RCCL, which stays outside
             # any capture: it runs eagerly
             for _ in range(steps):
-                self._decode_once(B, filtered, penalised)
+                self._decode_once(B, filtered, penalised, constrained)
             return
-        g = self._graphs.get(self._graph_key(B, filtered, penalised))
+        g = self._graphs.get(self._graph_key(B, filtered, penalised, constrained))
         if g is None:
-            g = self._capture(B, filtered, penalised)
+            g = self._capture(B, filtered, penalised, constrained)
         for _ in range(steps):
             g.replay()
 
-    def _graph_key(self, B: int, filtered: bool, penalised: bool = False) -> tuple:
+    def _graph_key(self, B: int, filtered: bool, penalised: bool = False, constrained: bool = False) -> tuple:
         """Key of a decode graph: (bucket, context class), (bucket, context class, True) for the graph
-        whose sampler filters, and (bucket, context class, filtered, "pen") for the graphs that penalise
-        first (all but the plain ones captured on first use; ``capture_graphs`` captures the plain ones)."""
+        whose sampler filters, (bucket, context class, filtered, "pen") for the graphs that penalise
+        first, and (bucket, context class, filtered, penalised, "con") for the graphs that constrain before
+        all that and finish with the rows' stop ids (all but the plain ones captured on first use;
+        ``capture_graphs`` captures the plain ones)."""
+        if constrained:
+            return (B, self._ctx_cls, filtered, penalised, "con")
         if penalised:
             return (B, self._ctx_cls, filtered, "pen")
         return (B, self._ctx_cls, True) if filtered else (B, self._ctx_cls)
@@ -560,7 +651,7 @@ class LLMEngine:
         self._sync()
         return n
 
-    def _capture(self, B: int, filtered: bool = False, penalised: bool = False):
+    def _capture(self, B: int, filtered: bool = False, penalised: bool = False, constrained: bool = False):
         # snapshot state rows the warm-up step will advance, run it eagerly once (lazy kernel-library
         # load, workspace and split-K ticket allocation), restore, then capture.
         st = self.state
@@ -568,17 +659,18 @@ class LLMEngine:
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
-            self._decode_once(B, filtered, penalised)  # (a filtered warm-up also allocates the filter workspace)
+            # (a filtered warm-up also allocates the filter workspace)
+            self._decode_once(B, filtered, penalised, constrained)
         torch.cuda.current_stream(self.device).wait_stream(s)
         for f, t in snap.items():
             getattr(st, f)[:B].copy_(t)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._decode_once(B, filtered, penalised)
+            self._decode_once(B, filtered, penalised, constrained)
         # capture does not execute; restore anyway in case the backend ran the work
         for f, t in snap.items():
             getattr(st, f)[:B].copy_(t)
-        self._graphs[self._graph_key(B, filtered, penalised)] = g
+        self._graphs[self._graph_key(B, filtered, penalised, constrained)] = g
         self.stats["graph_captures"] += 1
         return g
 
@@ -607,10 +699,11 @@ class LLMEngine:
         if len(prompts) != len(params):
             raise ValueError("prompts and params differ in length")
         for sp in params:
-            sp.validate()
+            sp.validate(self.cfg.vocab_size)
         eos = list(self.state.eos_ids)
         if ignore_eos:  # device-side stop set: captured graphs see it at replay (sampler.hip EOS_SLOTS)
             self.state.set_eos([])
+        self._ignore_eos = bool(ignore_eos)  # ... and the rows' own stop ids are written as -1s (_set_constraints)
         try:
             ar = self.model.custom_ar
             failed: Optional[BaseException] = None
@@ -642,6 +735,7 @@ class LLMEngine:
         finally:
             if ignore_eos:
                 self.state.set_eos(eos)
+            self._ignore_eos = False
         return out
 
     def _recover_custom_ar(self, prompts, params, imported, on_prefill, feeder, on_sync) -> List[GenOutput]:
@@ -677,7 +771,7 @@ class LLMEngine:
                              % (len(p), mn, self.max_model_len))
         if max(p) >= self.cfg.vocab_size or min(p) < 0:
             raise ValueError("token id out of range")
-        sp.validate()
+        sp.validate(self.cfg.vocab_size)
         return _Seq(i, p, replace(sp, max_new_tokens=mn), imported=imported)
 
     def _fit_ctx_class(self, seqs: Sequence[_Seq]) -> None:
@@ -698,7 +792,8 @@ class LLMEngine:
             if s.imported is not None:
                 tok = int(s.imported.first_token)
                 mn = s.params.max_new_tokens
-                if mn == 1 or tok in self.state.eos_ids:
+                own = () if self._ignore_eos else s.params.stop_token_ids
+                if mn == 1 or tok in self.state.eos_ids or tok in own:
                     results[i] = GenOutput([tok], len(s.prompt), "length" if mn == 1 else "stop")  # done at prefill
                     finished.append(i)
                     continue
@@ -736,12 +831,15 @@ class LLMEngine:
             # one readback: stop flags and steps left of every row
             snap = torch.stack((st.done[:n], st.max_new[:n] - st.gen_count[:n])).cpu()
             left = [int(r) for d, r in zip(snap[0].tolist(), snap[1].tolist()) if not d]
-            steps = self._window(left, feeder is not None or on_sync is not None or bool(prefilling))
+            # (a live row's own armed stop ids count like an armed EOS: the window is sync_every)
+            row_stops = not self._ignore_eos and any(s.params.stop_token_ids for s in active)
+            steps = self._window(left, feeder is not None or on_sync is not None or bool(prefilling) or row_stops)
             if steps:
                 t0 = time.perf_counter()
                 if t_window_end is not None:  # host work + prefill between two windows of running rows
                     self.stats["max_window_gap_s"] = max(self.stats.get("max_window_gap_s", 0.0), t0 - t_window_end)
-                self._decode_steps(B, steps, _any_filtered(active), _any_penalised(active))
+                self._decode_steps(B, steps, _any_filtered(active), _any_penalised(active),
+                                   _any_constrained(active))
                 self._sync()
                 t_window_end = time.perf_counter()
                 self.stats["decode_s"] += t_window_end - t0
@@ -771,7 +869,7 @@ class LLMEngine:
             del admitted
         return [r for r in results]  # type: ignore[return-value]
 
-    def _window(self, left: List[int], hooked: bool) -> int:
+    def _window(self, left: List[int], hooked: bool, row_stops: bool = False) -> int:
         """Decode steps to replay before the next host sync, given the steps ``left`` of every running row.
 
         Default: ``sync_every`` (a row may stop at an EOS id any step; the sync retires it and admits
@@ -784,7 +882,7 @@ class LLMEngine:
         left = [x for x in left if x > 0]
         if not left:
             return 0
-        if self.state.eos_ids or hooked:
+        if self.state.eos_ids or hooked or row_stops:  # (a live row's own armed stop ids count like an armed EOS)
             return min(self.sync_every, max(left))
         return min(MAX_WINDOW, min(left))
 
@@ -837,6 +935,7 @@ class LLMEngine:
             st.top_k[s.slot] = min(int(s.params.top_k), _I32_MAX)
             st.top_p[s.slot] = float(s.params.top_p)
             self._set_penalties(s.slot, s.params)
+            self._set_constraints(s.slot, s.params)
             st.result[s.slot] = 0
             if s.imported is not None:  # no forward pass: KV + first token come from elsewhere
                 self._install(s)
@@ -895,6 +994,19 @@ class LLMEngine:
         st.freq_pen[slot] = float(params.frequency_penalty)
         st.pres_pen[slot] = float(params.presence_penalty)
 
+    def _set_constraints(self, slot: int, params: SamplingParams) -> None:
+        """Constraint rows of ``slot``.  Under ``generate(ignore_eos=True)`` the row's stop ids are written as
+        -1s, as the engine's own are: pinned work stays pinned (and min_tokens has nothing to suppress)."""
+        st = self.state
+        items = params.bias_items()
+        st.bias_n[slot] = len(items)
+        if items:
+            st.bias_tok[slot, :len(items)].copy_(torch.tensor([int(t) for t, _ in items], dtype=torch.int32))
+            st.bias_val[slot, :len(items)].copy_(torch.tensor([float(x) for _, x in items], dtype=torch.float32))
+        st.min_new[slot] = int(params.min_tokens)
+        stops = [] if self._ignore_eos else [int(t) for t in params.stop_token_ids]
+        st.stop_ids[slot].copy_(torch.tensor(stops + [-1] * (MAX_STOP_IDS - len(stops)), dtype=torch.int32))
+
     def _setup_slot(self, s: _Seq, row: torch.Tensor) -> None:
         """Decode-state row of ``s`` at ``s.slot``: its pages, budget and sampling parameters."""
         st = self.state
@@ -907,6 +1019,7 @@ class LLMEngine:
         st.top_k[s.slot] = min(int(s.params.top_k), _I32_MAX)
         st.top_p[s.slot] = float(s.params.top_p)
         self._set_penalties(s.slot, s.params)
+        self._set_constraints(s.slot, s.params)
         st.result[s.slot] = 0
 
     def _interleaved_pass(self, prefilling: List[_Seq], active: List[_Seq], max_parts: Optional[int] = None) -> None:
@@ -1031,7 +1144,7 @@ class LLMEngine:
                 chunks[s.rid] = [torch.stack([k[:, :, g * hl:(g + 1) * hl], v[:, :, g * hl:(g + 1) * hl]])
                                  .reshape(-1) for g in range(groups)]
 
-        one = [replace(p, max_new_tokens=1) for p in params]
+        one = [replace(p, max_new_tokens=1, min_tokens=min(p.min_tokens, 1)) for p in params]
         outs = self.generate(prompts, one, ignore_eos=ignore_eos, on_prefill=grab)
         firsts = [o.token_ids[0] for o in outs]
         packs = [torch.cat([chunks[i][g] for i in range(len(prompts))]) if prompts else
@@ -1078,7 +1191,7 @@ class LLMEngine:
         import torch.distributed as dist
         if self.model.tp_size != 1 or self.model.hkv % world or self.kv.fp8:
             raise ValueError("prefill_export_cp needs a TP=1 bf16-KV engine and Hkv divisible by %d" % world)
-        s = self._new_seq(0, prompt, replace(params, max_new_tokens=1))
+        s = self._new_seq(0, prompt, replace(params, max_new_tokens=1, min_tokens=min(params.min_tokens, 1)))
         n = len(s.prompt)
         if n < 2 * world:
             raise ValueError("prompt of %d tokens is too short for context parallelism over %d ranks" % (n, world))
@@ -1096,6 +1209,7 @@ class LLMEngine:
             st.temps[0], st.seeds[0] = float(params.temperature), int(params.seed)
             st.top_k[0], st.top_p[0] = min(int(params.top_k), _I32_MAX), float(params.top_p)
             self._set_penalties(0, params)
+            self._set_constraints(0, s.params)
             slices = self.cp_slices(n, world)
             mine = [(b, e) for b, e in slices[rank] if e > b]
             if len(mine) != len(slices[rank]):  # n >= 2 world: every zigzag chunk holds a token

@@ -53,7 +53,8 @@ from typing import Any, Dict, List, Optional, Sequence
 
 from ..config import LLMConfig
 from ..parallel import dist as pdist
-from ..pipeline.providers import GenRequest, GenResult, Provider, request_filters, request_penalties
+from ..pipeline.providers import (GenRequest, GenResult, Provider, request_constraints, request_filters,
+                                  request_penalties)
 from .chat import render_chat, render_messages
 from .tokenizer import get_tokenizer
 
@@ -71,12 +72,15 @@ def _req_seed(base: int, req: GenRequest) -> int:
 def sampling_params(req: GenRequest, base_seed: int, config=None):
     """The engine's SamplingParams of one request: its budget and temperature, the seed derived from
     its text, its top-k / top-p filters (the request's own, else $TOP_K / $TOP_P of ``config``) and its
-    frequency / presence / repetition penalties (likewise)."""
+    frequency / presence / repetition penalties (likewise), its logit bias and minimum length (likewise) and
+    its stop token ids."""
     from .engine import SamplingParams
     top_k, top_p = request_filters(req, config)
     freq, pres, rep = request_penalties(req, config)
+    bias, min_tokens, stops = request_constraints(req, config)
     return SamplingParams(req.max_tokens, req.temperature, _req_seed(base_seed, req), top_k=top_k, top_p=top_p,
-                          frequency_penalty=freq, presence_penalty=pres, repetition_penalty=rep)
+                          frequency_penalty=freq, presence_penalty=pres, repetition_penalty=rep,
+                          logit_bias=bias or None, min_tokens=min_tokens, stop_token_ids=tuple(stops))
 
 
 def parse_parallel(spec: str, world: int) -> Dict[str, int]:

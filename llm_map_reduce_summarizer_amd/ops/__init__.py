@@ -220,7 +220,8 @@ def sample(logits, st, filtered=False):
     """Sample one token per row into decode state ``st``.  ``filtered``: some row may carry a top-k /
     top-p filter (``st.top_k`` / ``st.top_p``); every row's threshold is computed first (``st.thresh``,
     reference.nucleus_threshold) and tokens below it are left out.  Rows without a filter sample exactly
-    as with ``filtered`` False."""
+    as with ``filtered`` False.  ``st.constrained`` set (a batch with a constrained row): a row is also
+    retired when its new token is one of its own ``st.stop_ids``."""
     if _use_hip(logits):
         from . import hip
         return hip.sample(logits, st, filtered=filtered)
@@ -244,6 +245,20 @@ def penalize(logits, st, tok_offset=0):
     n = logits.shape[0]
     return reference.apply_penalties(logits, st.out_tokens[:n], st.gen_count[:n], st.rep_pen[:n], st.freq_pen[:n],
                                      st.pres_pen[:n], st.done[:n], tok_offset)
+
+
+def constrain(logits, st, tok_offset=0):
+    """Logit bias and minimum length of decode state ``st`` (``bias_tok`` / ``bias_val`` / ``bias_n`` /
+    ``min_new`` / ``stop_ids`` rows and the ``eos`` slots) applied in place to the bf16 rows ``logits``,
+    before the penalties and the sampler: reference.apply_constraints.  ``logits`` may be a vocabulary
+    shard whose first column is token ``tok_offset``.  (The row stop ids themselves are honoured by
+    ``sample`` / ``sample_tp`` when ``st.constrained`` is set.)"""
+    if _use_hip(logits):
+        from . import hip
+        return hip.constrain(logits, st, tok_offset)
+    n = logits.shape[0]
+    return reference.apply_constraints(logits, st.bias_tok[:n], st.bias_val[:n], st.bias_n[:n], st.gen_count[:n],
+                                       st.min_new[:n], st.stop_ids[:n], st.eos, st.done[:n], tok_offset)
 
 
 def sample_tp(logits, st, tok_offset, max_reduce):

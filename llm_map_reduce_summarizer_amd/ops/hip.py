@@ -60,6 +60,9 @@ _SIGS = {
                      _vp],
     "mrsum_penalize": [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp],
     "mrsum_penalize_scan": [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mrsum_constrain": [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mrsum_sample_finish_stops": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _c_int, _vp],
+    "mrsum_sample_keys_filtered": [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mrsum_sample_thresh": [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mrsum_sample_filtered": [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                               _vp, _vp, _c_int, _vp, _vp, _vp],
@@ -630,24 +633,39 @@ def sample_thresholds(logits: torch.Tensor, st) -> torch.Tensor:
 def sample(logits: torch.Tensor, st, filtered: bool = False) -> None:
     """Sample one token per row of ``logits`` into decode state ``st`` (see engine.state).  ``filtered``
     and ``st`` carrying ``top_k`` / ``top_p`` / ``thresh`` rows: the top-k / top-p path (histogram,
-    threshold, Gumbel-max over the kept tokens); otherwise the plain sampler, the same launch as ever."""
+    threshold, Gumbel-max over the kept tokens); otherwise the plain sampler, the same launch as ever.
+    ``st.constrained`` set: the same keys, ended by the finish that also retires a row at one of its own
+    ``st.stop_ids``."""
     _bf16_cuda(logits)
     _rows_ok(logits)
     B, V = logits.shape
     _req(st.temps.numel() >= B and st.next_ids.numel() >= B and st.out_tokens.shape[0] >= B,
          "sample: state smaller than batch")
     _eos_ok(st)
+    row_stops = getattr(st, "constrained", False)
+    if row_stops:
+        _stop_ids_ok(st, B)
     if filtered:
         _req(all(hasattr(st, f) for f in ("top_k", "top_p", "thresh")),
              "sample: a filtered batch needs top_k / top_p / thresh rows in the state")
         _filter_fields_ok(st, B)
         hist = _filter_hist(st, B, logits.device)
+        if row_stops:
+            _check(_fn("mrsum_sample_keys_filtered")(_p(logits), logits.stride(0), B, V, _p(st.temps), _p(st.seeds),
+                                                     _p(st.positions), _p(st.top_k), _p(st.top_p), _p(st.done),
+                                                     _p(st.thresh), _p(hist), _p(st.result), _stream()),
+                   "sample_keys_filtered")
+            return _finish_stops(st, B)
         _check(_fn("mrsum_sample_filtered")(_p(logits), logits.stride(0), B, V, _p(st.temps), _p(st.seeds),
                                             _p(st.positions), _p(st.top_k), _p(st.top_p), _p(st.thresh), _p(hist),
                                             _p(st.result), _p(st.next_ids), _p(st.positions), _p(st.gen_count),
                                             _p(st.max_new), _p(st.out_tokens), st.out_tokens.stride(0), _p(st.done),
                                             _p(st.eos), _stream()), "sample_filtered")
         return
+    if row_stops:
+        _check(_fn("mrsum_sample_keys")(_p(logits), logits.stride(0), B, V, 0, _p(st.temps), _p(st.seeds),
+                                        _p(st.positions), _p(st.result), _stream()), "sample_keys")
+        return _finish_stops(st, B)
     _check(_fn("mrsum_sample")(_p(logits), logits.stride(0), B, V, _p(st.temps), _p(st.seeds), _p(st.positions),
                                _p(st.result), _p(st.next_ids), _p(st.positions), _p(st.gen_count), _p(st.max_new),
                                _p(st.out_tokens), st.out_tokens.stride(0), _p(st.done), _p(st.eos),
@@ -690,6 +708,56 @@ def penalize(logits: torch.Tensor, st, tok_offset: int = 0, form: str = "table")
     return logits
 
 
+CONSTRAIN_MAX_BIAS = 300  # bias entries per row (OpenAI's limit); sampler.hip runs one thread per entry
+STOP_SLOTS = 4  # sampler.hip STOP_SLOTS: stop ids per row, -1 = unused
+
+
+def _stop_ids_ok(st, B: int) -> None:
+    _req(hasattr(st, "stop_ids"), "sample: a constrained batch needs stop_ids rows in the state")
+    t = st.stop_ids
+    _req(t.is_cuda and t.dtype == torch.int32 and t.dim() == 2 and t.shape[1] == STOP_SLOTS and t.is_contiguous()
+         and t.shape[0] >= B and t.data_ptr() % 16 == 0,
+         "sample: stop_ids must be contiguous, 16-byte aligned int32 device rows of 4 slots")
+
+
+def _finish_stops(st, B: int) -> None:
+    _check(_fn("mrsum_sample_finish_stops")(_p(st.result), _p(st.next_ids), _p(st.positions), _p(st.gen_count),
+                                            _p(st.max_new), _p(st.out_tokens), st.out_tokens.stride(0), _p(st.done),
+                                            _p(st.eos), _p(st.stop_ids), B, _stream()), "sample_finish_stops")
+
+
+def _constraint_fields_ok(st, B: int) -> None:
+    _req(all(hasattr(st, f) for f in ("bias_tok", "bias_val", "bias_n", "min_new", "stop_ids")),
+         "constrain: the state needs bias_tok / bias_val / bias_n / min_new / stop_ids rows")
+    bt, bv = st.bias_tok, st.bias_val
+    _req(bt.is_cuda and bt.dtype == torch.int32 and bt.dim() == 2 and bt.is_contiguous() and bt.shape[0] >= B,
+         "constrain: bias_tok must be contiguous int32 device rows of the batch")
+    _req(bv.is_cuda and bv.dtype == torch.float32 and bv.is_contiguous() and bv.shape == bt.shape,
+         "constrain: bias_val must be contiguous float32 device rows shaped like bias_tok")
+    _req(st.bias_n.numel() >= B and st.min_new.numel() >= B and st.gen_count.numel() >= B and st.done.numel() >= B,
+         "constrain: state smaller than batch")
+    _i32(st.bias_n, st.min_new, st.gen_count, st.done)
+    _stop_ids_ok(st, B)
+    _eos_ok(st)
+
+
+def constrain(logits: torch.Tensor, st, tok_offset: int = 0) -> torch.Tensor:
+    """Logit bias and minimum length in place on ``logits`` [B, V] (reference.apply_constraints): row b's
+    first ``st.bias_n[b]`` entries of (``st.bias_tok[b]``, ``st.bias_val[b]``) that fall into the columns'
+    token range [tok_offset, tok_offset + V) are biased (or banned, bias -inf), then, while
+    ``st.gen_count[b] < st.min_new[b]``, the armed stop ids (``st.eos`` and ``st.stop_ids[b]``) are set to
+    -inf; neutral and done rows are left alone.  One launch, no workspace, capturable."""
+    _bf16_cuda(logits)
+    _req(logits.dim() == 2 and logits.stride(1) == 1, "constrain: expected 2-D row-major logits")
+    B, V = logits.shape
+    _req(tok_offset >= 0, "constrain: negative tok_offset")
+    _constraint_fields_ok(st, B)
+    _check(_fn("mrsum_constrain")(_p(logits), logits.stride(0), B, V, int(tok_offset), _p(st.bias_tok),
+                                  _p(st.bias_val), st.bias_tok.stride(0), _p(st.bias_n), _p(st.gen_count),
+                                  _p(st.min_new), _p(st.stop_ids), _p(st.eos), _p(st.done), _stream()), "constrain")
+    return logits
+
+
 def sample_tp(logits: torch.Tensor, st, tok_offset: int, max_reduce) -> None:
     """Vocab-parallel sampling: Gumbel-max keys over this rank's logits shard (global token ids =
     tok_offset + column), ``max_reduce(keys)`` across the TP group (in place, unsigned), then the
@@ -703,6 +771,9 @@ def sample_tp(logits: torch.Tensor, st, tok_offset: int, max_reduce) -> None:
     _check(_fn("mrsum_sample_keys")(_p(logits), logits.stride(0), B, V, tok_offset, _p(st.temps), _p(st.seeds),
                                     _p(st.positions), _p(st.result), _stream()), "sample_keys")
     max_reduce(st.result[:B])
+    if getattr(st, "constrained", False):  # every rank holds the same stop_ids: the same finish on all
+        _stop_ids_ok(st, B)
+        return _finish_stops(st, B)
     _check(_fn("mrsum_sample_finish")(_p(st.result), _p(st.next_ids), _p(st.positions), _p(st.gen_count),
                                       _p(st.max_new), _p(st.out_tokens), st.out_tokens.stride(0), _p(st.done),
                                       _p(st.eos), B, _stream()), "sample_finish")

@@ -458,6 +458,49 @@ def apply_penalties(logits: torch.Tensor, out_tokens, gen_count, rep, freq, pres
     return logits
 
 
+def apply_constraints(logits: torch.Tensor, bias_tok, bias_val, bias_n, gen_count, min_new, stop_ids, eos,
+                      done=None, tok_offset: int = 0) -> torch.Tensor:
+    """Logit bias and minimum length, in place on the bf16 rows ``logits`` [B, V] (returned), before the
+    penalties and before any filter.
+
+    Bias: for every entry i < ``bias_n[b]`` of row b whose column ``bias_tok[b, i] - tok_offset`` lies in
+    [0, V) (the tokens of a row are distinct; the host guarantees it):
+
+        finite bias:  x = float32(logit);  x = x + bias (one rounded fp32 add);  logit = bf16(x)  (RNE)
+        bias -inf:    a ban -- the entry is STORED as -inf, not added, so a +inf logit is banned too and no
+                      NaN appears.  A NaN logit stays a NaN either way.
+
+    Minimum length: with ``gen_count[b] < min_new[b]`` every armed stop id -- the engine's four ``eos`` slots
+    and the row's four ``stop_ids[b]``, -1 = unused slot -- that falls into the shard is stored as -inf;
+    this wins over a bias on the same token.  With ``gen_count[b] >= min_new[b]`` nothing is suppressed.
+
+    Every other entry keeps its bits; a row with ``bias_n`` 0 and nothing to suppress, or with ``done`` set,
+    is untouched.  ``tok_offset`` / V describe a vocabulary shard: constraining the shards of a row one by
+    one equals constraining the whole row.  sampler.hip's constrain kernel matches it bit for bit."""
+    B, V = logits.shape
+    ninf = torch.tensor(float("-inf"), dtype=logits.dtype, device=logits.device)
+    armed = [int(x) for x in eos.tolist() if int(x) >= 0]
+    for b in range(B):
+        n = min(int(bias_n[b]), bias_tok.shape[1])
+        suppress = int(gen_count[b]) < int(min_new[b])
+        if (n <= 0 and not suppress) or (done is not None and int(done[b])):
+            continue
+        if n > 0:
+            cols = bias_tok[b, :n].to(torch.int64) - int(tok_offset)
+            vals = bias_val[b, :n].to(torch.float32)
+            keep = (cols >= 0) & (cols < V)
+            cols, vals = cols[keep].to(logits.device), vals[keep].to(logits.device)
+            x = logits[b, cols].to(torch.float32)
+            ban = torch.isneginf(vals)
+            y = (x + torch.where(ban, torch.zeros_like(vals), vals)).to(logits.dtype)
+            logits[b, cols] = torch.where(ban & ~torch.isnan(x), ninf, y)
+        if suppress:
+            for t in armed + [int(x) for x in stop_ids[b].tolist() if int(x) >= 0]:
+                if 0 <= t - int(tok_offset) < V:
+                    logits[b, t - int(tok_offset)] = ninf
+    return logits
+
+
 def sample_tokens(logits: torch.Tensor, temps: torch.Tensor, seeds: torch.Tensor,
                   positions: torch.Tensor, thresh: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Gumbel-max sampling (argmax when temperature <= 0); ties -> lowest id.  ``thresh`` (fp32 [B],
@@ -477,9 +520,11 @@ def sample_tokens(logits: torch.Tensor, temps: torch.Tensor, seeds: torch.Tensor
 
 
 def sample_finish(tokens: torch.Tensor, st) -> None:
-    """Bookkeeping identical to the finish kernel (st = engine DecodeState)."""
+    """Bookkeeping identical to the finish kernel (st = engine DecodeState).  A state whose
+    ``constrained`` flag is set also retires a row at one of its own ``stop_ids`` (-1 = unused slot)."""
     B = tokens.shape[0]
     eos = set(int(x) for x in st.eos.tolist() if int(x) >= 0)
+    row_stops = getattr(st, "constrained", False)
     for b in range(B):
         if int(st.done[b]):
             continue
@@ -488,7 +533,8 @@ def sample_finish(tokens: torch.Tensor, st) -> None:
         st.out_tokens[b, g] = tok
         st.gen_count[b] = g + 1
         st.next_ids[b] = tok
-        if g + 1 >= int(st.max_new[b]) or tok in eos:
+        own = row_stops and tok in [int(x) for x in st.stop_ids[b].tolist()]  # tok >= 0 never matches -1
+        if g + 1 >= int(st.max_new[b]) or tok in eos or own:
             st.done[b] = 1
         else:
             st.positions[b] += 1

@@ -26,7 +26,7 @@ import random
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
-from ..config import LLMConfig
+from ..config import LLMConfig, parse_logit_bias
 
 log = logging.getLogger("mrsum.providers")
 
@@ -50,6 +50,59 @@ class GenRequest:
     frequency_penalty: Optional[float] = None
     presence_penalty: Optional[float] = None
     repetition_penalty: Optional[float] = None
+    # constraints on token ids of the LOCAL tokenizer (engine SamplingParams): logit_bias as a list of
+    # [token, bias] pairs, a bias a number in [-100, 100] or "ban" (-inf) -- a list, and "ban" spelled out,
+    # so that the request survives the serve path's JSON broadcast (object keys would turn into strings, -inf
+    # is no JSON number); a {token: bias} mapping is accepted too (request_constraints normalises both).
+    # None = the configured default ($LOGIT_BIAS / $MIN_NEW_TOKENS: none / 0); stop_token_ids has none
+    logit_bias: Any = None
+    min_tokens: Optional[int] = None
+    stop_token_ids: Optional[List[int]] = None
+
+
+def logit_bias_pairs(lb: Any) -> List[Tuple[int, float]]:
+    """A logit bias in any accepted form -- {token: bias}, [(token, bias)], tokens as integers or decimal
+    strings, a bias a number, "ban" or None (a ban) -- as [(token, bias)] with -inf for a ban.  Raises
+    ValueError for anything else; ranges are SamplingParams.validate's business."""
+    if not lb:
+        return []
+    if not isinstance(lb, (dict, list, tuple)):
+        raise ValueError("logit_bias must map token ids to biases, got %r" % (lb,))
+    out = []
+    for item in (lb.items() if isinstance(lb, dict) else lb):
+        if not isinstance(item, (list, tuple)) or len(item) != 2:
+            raise ValueError("logit_bias entries must be (token, bias) pairs, got %r" % (item,))
+        t, x = item
+        if isinstance(t, str) and t.strip().lstrip("+").isdigit():
+            t = int(t)
+        if isinstance(t, bool) or not isinstance(t, int):
+            raise ValueError("logit_bias token ids must be integers, got %r" % (t,))
+        if x is None or (isinstance(x, str) and x.strip().lower() == "ban"):
+            x = float("-inf")
+        if isinstance(x, bool) or not isinstance(x, (int, float)):
+            raise ValueError("a logit bias must be a number or \"ban\", got %r" % (x,))
+        out.append((t, float(x)))
+    return out
+
+
+def logit_bias_json(lb: Any) -> List[list]:
+    """``logit_bias_pairs`` in the JSON-safe form GenRequest carries: [[token, bias | "ban"]]."""
+    return [[t, "ban" if x == float("-inf") else x] for t, x in logit_bias_pairs(lb)]
+
+
+def request_constraints(req: GenRequest, config: Optional[LLMConfig]) -> Tuple[List[Tuple[int, float]], int, List[int]]:
+    """(logit_bias pairs, min_tokens, stop_token_ids) of a request: its own values, else the configured
+    defaults ($LOGIT_BIAS / $MIN_NEW_TOKENS; none / 0 = off).  A configured minimum is capped at the request's
+    max_tokens (a request's own is checked against it by SamplingParams.validate)."""
+    if req.logit_bias is not None:
+        bias = logit_bias_pairs(req.logit_bias)
+    else:
+        bias = parse_logit_bias(getattr(config, "LOGIT_BIAS", "") or "")
+    if req.min_tokens is not None:
+        m = req.min_tokens
+    else:
+        m = min(int(getattr(config, "MIN_NEW_TOKENS", 0)), int(req.max_tokens))
+    return bias, m, list(req.stop_token_ids or ())
 
 
 def request_filters(req: GenRequest, config: Optional[LLMConfig]) -> Tuple[int, float]:
@@ -215,6 +268,8 @@ class OpenAIProvider(_HTTPProvider):
             body["frequency_penalty"] = freq
         if pres != 0.0:
             body["presence_penalty"] = pres
+        # logit_bias / min_tokens / stop_token_ids name token ids of the LOCAL tokenizer, which mean nothing
+        # to a hosted model: none of the three is sent
         data = await self._post(headers, body)
         usage = data.get("usage", {})
         pt, ct = usage.get("prompt_tokens", 0), usage.get("completion_tokens", 0)
@@ -242,7 +297,8 @@ class AnthropicProvider(_HTTPProvider):
             body["top_p"] = top_p
         if top_k > 0:
             body["top_k"] = top_k
-        # (the Anthropic API has no frequency / presence / repetition penalty: none is sent)
+        # (the Anthropic API has no frequency / presence / repetition penalty: none is sent; logit_bias /
+        # min_tokens / stop_token_ids name ids of the LOCAL tokenizer and are sent to no hosted API)
         data = await self._post(headers, body)
         text = data["content"][0]["text"]
         usage = data.get("usage") or {}

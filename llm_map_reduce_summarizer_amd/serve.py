@@ -17,7 +17,11 @@ message as one event.  ``top_p`` (both endpoints) and ``top_k`` (``/v1/messages`
 the common extension) restrict the sample on the GPU (sampler.hip's filter kernels); a value out of range
 or not a number is a 400.  ``frequency_penalty`` / ``presence_penalty`` (numbers in [-2, 2], the OpenAI
 range) and ``repetition_penalty`` (the common extension, a number in (0, 2]) act on the tokens generated so
-far (sampler.hip's penalize kernel), on both endpoints; anything else is a 400.  Stop sequences and n > 1 are not supported (400).
+far (sampler.hip's penalize kernel), on both endpoints; anything else is a 400.  ``logit_bias`` (an object
+from token id to a number in [-100, 100], at most 300 entries), ``min_tokens`` (an integer in [0, max tokens])
+and ``stop_token_ids`` (at most 4 token ids, the vLLM extension) constrain the sample on the GPU (sampler.hip's
+constrain kernel and its finish with row stop ids), on both endpoints; token ids are the served model's, and
+anything else is a 400.  Stop sequences and n > 1 are not supported (400).
 
 Batching: HTTP handlers only enqueue; one engine thread owns the engine.  Single process
 (``ContinuousBatcher``): the first requests start a generate and every request that arrives while it runs
@@ -117,7 +121,45 @@ def _penalties(body: Dict[str, Any]) -> Dict[str, Any]:
     return out
 
 
-def openai_request(body: Dict[str, Any], default_temp: float = 1.0) -> GenRequest:
+def _token_id(t: Any, vocab: Optional[int]) -> Optional[int]:
+    """A token id given as an integer or a decimal string, None when it is neither or out of range."""
+    if isinstance(t, str) and t.strip().isdigit():
+        t = int(t)
+    if isinstance(t, bool) or not isinstance(t, int) or t < 0 or (vocab is not None and t >= vocab):
+        return None
+    return t
+
+
+def _constraints(body: Dict[str, Any], max_tokens: int, vocab: Optional[int] = None) -> Dict[str, Any]:
+    """``logit_bias`` / ``min_tokens`` / ``stop_token_ids`` of a request body as GenRequest fields (absent or
+    null: the server's default).  ``vocab``: the served model's vocabulary size, when known."""
+    out: Dict[str, Any] = {}
+    lb, m, stops = body.get("logit_bias"), body.get("min_tokens"), body.get("stop_token_ids")
+    if lb is not None:
+        if not isinstance(lb, dict) or len(lb) > 300:
+            raise BadRequest("logit_bias must be an object of at most 300 token ids mapped to biases")
+        pairs: Dict[int, float] = {}
+        for k, x in lb.items():
+            t = _token_id(k, vocab)
+            if t is None or t in pairs:
+                raise BadRequest("logit_bias keys must be distinct token ids of the served model, got %r" % (k,))
+            if isinstance(x, bool) or not isinstance(x, (int, float)) or not -100.0 <= float(x) <= 100.0:  # NaN fails
+                raise BadRequest("logit_bias values must be numbers in [-100, 100]")
+            pairs[t] = float(x)
+        out["logit_bias"] = [[t, x] for t, x in pairs.items()]
+    if m is not None:
+        if isinstance(m, bool) or not isinstance(m, int) or not 0 <= m <= max_tokens:
+            raise BadRequest("min_tokens must be an integer in [0, max tokens]")
+        out["min_tokens"] = m
+    if stops is not None:
+        if not isinstance(stops, list) or len(stops) > 4 or any(_token_id(t, vocab) is None or isinstance(t, str)
+                                                                for t in stops):
+            raise BadRequest("stop_token_ids must be at most 4 token ids of the served model")
+        out["stop_token_ids"] = [int(t) for t in stops]
+    return out
+
+
+def openai_request(body: Dict[str, Any], default_temp: float = 1.0, vocab: Optional[int] = None) -> GenRequest:
     """GenRequest of an OpenAI ``/v1/chat/completions`` body.  A [system?, user] chat keeps the
     reference's request shape (same prompt rendering and seed as the in-process provider)."""
     msgs = body.get("messages")
@@ -132,7 +174,7 @@ def openai_request(body: Dict[str, Any], default_temp: float = 1.0) -> GenReques
             raise BadRequest("unsupported message role %r" % role)
         turns.append({"role": role, "content": _text(m.get("content", ""))})
     max_tokens, temp = _common(body, default_temp)
-    filters = {**_filters(body), **_penalties(body)}
+    filters = {**_filters(body), **_penalties(body), **_constraints(body, max_tokens, vocab)}
     roles = [t["role"] for t in turns]
     if roles in (["user"], ["system", "user"]):
         return GenRequest(user=turns[-1]["content"], system=turns[0]["content"] if len(turns) == 2 else None,
@@ -141,7 +183,7 @@ def openai_request(body: Dict[str, Any], default_temp: float = 1.0) -> GenReques
                       messages=turns, **filters)
 
 
-def anthropic_request(body: Dict[str, Any], default_temp: float = 1.0) -> GenRequest:
+def anthropic_request(body: Dict[str, Any], default_temp: float = 1.0, vocab: Optional[int] = None) -> GenRequest:
     """GenRequest of an Anthropic ``/v1/messages`` body (top-level ``system``)."""
     msgs = body.get("messages")
     if not isinstance(msgs, list) or not msgs:
@@ -155,7 +197,7 @@ def anthropic_request(body: Dict[str, Any], default_temp: float = 1.0) -> GenReq
             raise BadRequest("unsupported message role %r" % role)
         turns.append({"role": role, "content": _text(m.get("content", ""))})
     max_tokens, temp = _common(body, default_temp)
-    filters = {**_filters(body), **_penalties(body)}
+    filters = {**_filters(body), **_penalties(body), **_constraints(body, max_tokens, vocab)}
     if [t["role"] for t in turns[-1:]] != ["user"]:
         raise BadRequest("the last message must be from the user")
     if len(msgs) == 1:
@@ -340,6 +382,8 @@ class ContinuousBatcher(Batcher):
                         if req.max_tokens >= prov.max_model_len:
                             raise BadRequest("max_tokens must be below max_model_len (%d)" % prov.max_model_len)
                         ids = prov.encode_request(req)
+                        sp = sampling_params(req, prov.seed, prov.config)
+                        sp.validate(prov.engine.cfg.vocab_size)
                     except Exception as e:  # noqa: BLE001 -- this client only
                         self._resolve(lp, fut, GenResult("", error="%s: %s" % (type(e).__name__, e)))
                         continue
@@ -347,7 +391,7 @@ class ContinuousBatcher(Batcher):
                     if len(it) > 3:
                         sent[nxt[0]] = 0
                     nxt[0] += 1
-                    out.append((ids, sampling_params(req, prov.seed, prov.config)))
+                    out.append((ids, sp))
                     self.stats["requests"] += 1
                 return out
 
@@ -480,12 +524,18 @@ def build_app(batcher: Batcher, model_name: str, api_key: Optional[str] = None, 
         token = auth[7:] if auth.startswith("Bearer ") else request.headers.get("x-api-key", "")
         return hmac.compare_digest(token.encode(), api_key.encode())  # constant-time
 
+    # the served model's vocabulary size, when the batcher's provider knows its model (asked of the model's
+    # configuration: no engine is built for it): token ids in a request (logit_bias, stop_token_ids) are
+    # checked against it here, so a bad id is this client's 400
+    model_config = getattr(getattr(batcher, "provider", None), "model_config", None)
+    vocab = getattr(model_config(), "vocab_size", None) if callable(model_config) else None
+
     async def _serve(request: Request, parse, render):
         if not _authorised(request):
             return _err(401, "invalid API key", "authentication_error")
         try:
             body = await request.json()
-            req = parse(body, default_temp)
+            req = parse(body, default_temp, vocab)
         except BadRequest as e:
             return _err(400, str(e), "invalid_request_error")
         except (ValueError, TypeError, AttributeError) as e:

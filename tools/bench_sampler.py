@@ -17,6 +17,13 @@ tokens (half as many distinct ids), in both forms of the kernel's token reductio
 open-addressing table the engine runs) and ``scan`` (the ownership scan).
 
     python tools/bench_sampler.py --penalties --bs 1,10,39 > profiles/sampler_penalties.jsonl
+
+``--constraints``: the cost of the constrain launch (ops.hip.constrain, which a constrained decode step runs
+before the penalties and the sampler), timed the same way, for every row carrying ``entries`` logit-bias
+entries (a quarter of them bans) and a minimum length that suppresses its armed stop ids; ``neutral`` is the
+same launch over rows with nothing to do (every workgroup exits at once).
+
+    python tools/bench_sampler.py --constraints --bs 1,10,39 > profiles/sampler_constraints.jsonl
 """
 import argparse
 import json
@@ -34,6 +41,8 @@ ap.add_argument("--temperature", type=float, default=0.3)
 ap.add_argument("--scale", type=float, default=3.0, help="std of the random logits")
 ap.add_argument("--penalties", action="store_true", help="time the penalize launch instead of the filter")
 ap.add_argument("--gen-counts", default="1,256,2048", help="--penalties: generated tokens per row")
+ap.add_argument("--constraints", action="store_true", help="time the constrain launch instead of the filter")
+ap.add_argument("--entries", default="1,300", help="--constraints: logit-bias entries per row")
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.tree))
 
@@ -109,6 +118,32 @@ for B in (int(b) for b in args.bs.split(",")):
                 d = [timed(step, args.iters) - timed(rewrite, args.iters) for _ in range(args.repeats)]
                 rec["penalize_%s_us" % form] = round(statistics.median(d), 2)
                 rec["penalize_%s_us_min_max" % form] = [round(min(d), 2), round(max(d), 2)]
+            print(json.dumps(rec), flush=True)
+        continue
+
+    if args.constraints:
+        for n in (int(x) for x in args.entries.split(",")):
+            st = State(B, 8, [0] * B, [1.0] * B)
+            st.eos = torch.tensor([128001, 128009, -1, -1], dtype=torch.int32, device=dev) % args.vocab
+            st.bias_tok = torch.stack([torch.randperm(args.vocab, generator=g)[:300] for _ in range(B)]).to(
+                torch.int32).to(dev)
+            vals = torch.rand(B, 300, generator=g) * 200.0 - 100.0
+            vals[torch.rand(B, 300, generator=g) < 0.25] = float("-inf")
+            st.bias_val = vals.to(dev)
+            st.stop_ids = torch.randint(0, args.vocab, (B, 4), generator=g).to(torch.int32).to(dev)
+            rec = {"B": B, "V": args.vocab, "entries": n, "iters": args.iters, "repeats": args.repeats}
+            for mode, (bn, mn) in (("constrain", (n, 1)), ("neutral", (0, 0))):
+                st.bias_n = torch.full((B,), bn, dtype=torch.int32, device=dev)
+                st.min_new = torch.full((B,), mn, dtype=torch.int32, device=dev)  # gen_count is 0
+
+                def step(i, st=st):
+                    rewrite(i)
+                    hip.constrain(logits, st)
+
+                timed(step, args.iters)
+                d = [timed(step, args.iters) - timed(rewrite, args.iters) for _ in range(args.repeats)]
+                rec["%s_us" % mode] = round(statistics.median(d), 2)
+                rec["%s_us_min_max" % mode] = [round(min(d), 2), round(max(d), 2)]
             print(json.dumps(rec), flush=True)
         continue
 
