@@ -742,3 +742,267 @@ MRSUM_API int mrsum_stream_fp8(const void* x, int ldx, const void* W, const floa
 #undef L8
     return (int)hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------
+// p14: bf16 decode weights stored losslessly in 14 bits.  A bf16 weight w splits into lo = w & 0xff
+// (exponent bit 0 | 7 mantissa bits), kept verbatim, and hi = w >> 8 (sign | exponent bits 7..1), kept as
+// a 6-bit code (sign << 5) | c5 with e7 = hi & 0x7f: c5 = 0 for e7 = 0 (+-0, the subnormals and the smallest
+// normals -- torch's CPU normal generator emits exact zeros, ~4 in 2^24, so the project's own initialisation
+// needs them) and c5 = e7 - base7 + 1 in 1..31 otherwise, base7 = max(max e7 of the matrix - 30, 1): a window
+// of 31 e7 values = 62 binades below the largest element, which joins the zero class whenever the maximum
+// allows.  A matrix is packable iff every e7 is 0 or in the window; hi = sign << 7 | (c5 ? c5 + base7 - 1 : 0)
+// then decodes to exactly the original bits.  12.5 % fewer weight bytes per decode step.
+//
+// Storage (private to this file; ops/reference.py p14_pack_ref mirrors it bit for bit): one 3584-byte tile
+// per (16-row group G, 128-wide k block kb), tiles of a group consecutive over kb, so a wave streams one
+// contiguous range and any workgroup width reads the same tensor.  A tile is the wave's LDS image, copied
+// linearly by 3 x global_load_lds 16 B/lane + 2 x 4 B/lane (five DMA instructions per wave per slot; the
+// 12 B/lane form, 2 x 768 B for the code planes, did not produce this linear image on the hardware: the
+// first build's products were wrong with a packer that matched the reference).  Lane l = 16 g + r owns the 32 weights W[16 G + r][128 kb + 32 i + 8 g + e] (i < 4, e < 8) --
+// its A fragments of the 4 MFMA steps, at the k positions of the bf16 kernel, so x and the accumulation
+// order are unchanged and the output is bit-identical:
+//   [   0, 2048) lo plane : half h = i >> 1 at h * 1024 + 16 l, byte 8 (i & 1) + e     (2 ds_read_b128)
+//   [2048, 3072) 4-bit plane: 16 l + 4 i + b = code bits 3..0 of e = b | of e = 4 + b << 4 (1 ds_read_b128)
+//   [3072, 3584) 2-bit plane: 8 l + 4 h = one dword per half; with q = 2 (i & 1) + (e >> 2), b = e & 3:
+//                code bit 4 at bit 8 b + 4 - q, sign at bit 8 b + 7 - {0, 1, 2, 7}[q]      (1 ds_read_b64)
+// so that decode is whole-dword mask / shift / add and four v_perm_b32 per MFMA step.
+namespace {
+constexpr int P14_TILE = 3584, P14_NIB = 2048, P14_TWO = 3072;
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+
+template <int AUX = 0>
+__device__ __forceinline__ void glds4(const void* g, char* lds) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+                                     (__attribute__((address_space(3))) void*)lds, 4, 0, AUX);
+}
+
+// hi bytes of 4 weights: q4 = their 4-bit codes one per byte, s2 = the half's 2-bit dword, Q = 2 (i & 1) + (e >> 2)
+template <int Q>
+__device__ __forceinline__ uint32_t p14_hi4(uint32_t q4, uint32_t s2, uint32_t base4) {
+    constexpr int SS = Q == 3 ? 7 : Q;
+    const uint32_t c5 = q4 | ((s2 << Q) & 0x10101010u);
+    const uint32_t nz = (c5 + 0x1f1f1f1fu) & 0x20202020u;  // bit 5 of a byte: its code is not 0
+    const uint32_t on = (nz << 3) - (nz >> 5);              // 0xff in those bytes (2^(8b+8) - 2^(8b) each)
+    return (c5 + (on & base4)) | ((s2 << SS) & 0x80808080u);
+}
+
+// A fragment of MFMA step i: l0 / l1 = lo bytes of e = 0..3 / 4..7, nb = the step's 4-bit dword
+template <int PAR>
+__device__ __forceinline__ bf16x8 p14_frag(uint32_t l0, uint32_t l1, uint32_t nb, uint32_t s2, uint32_t base4) {
+    const uint32_t h0 = p14_hi4<2 * PAR>(nb & 0x0f0f0f0fu, s2, base4);
+    const uint32_t h1 = p14_hi4<2 * PAR + 1>((nb >> 4) & 0x0f0f0f0fu, s2, base4);
+    const u32x4 o = {__builtin_amdgcn_perm(h0, l0, 0x05010400u), __builtin_amdgcn_perm(h0, l0, 0x07030602u),
+                     __builtin_amdgcn_perm(h1, l1, 0x05010400u), __builtin_amdgcn_perm(h1, l1, 0x07030602u)};
+    return __builtin_bit_cast(bf16x8, o);
+}
+}  // namespace
+
+template <int MT, int EPI, int WPB>
+__global__ __launch_bounds__(64 * WPB, 1) void stream_p14_kernel(const bf16* __restrict__ x, int ldx,
+                                                                 const unsigned char* __restrict__ W, int base7,
+                                                                 int K, int M, void* __restrict__ out, int ldo,
+                                                                 int kper, float* __restrict__ parts,
+                                                                 int* __restrict__ counters, const NormArgs e) {
+    constexpr int R = 16 * WPB, BM = 16 * MT;
+    constexpr int WBYTES = WPB * P14_TILE, SLOT = WBYTES + BM * 256;
+    // the slot is 12.5 % smaller than the bf16 one: a deeper ring keeps the weight bytes in flight (cap 8, as
+    // the fp8 one-row variant)
+    constexpr int D = (LDS_BUDGET / SLOT) < 8 ? (LDS_BUDGET / SLOT) : 8;
+    static_assert(D >= 2, "ring too shallow");
+    constexpr int XP = 2 * BM / 8;
+    constexpr int XI = (XP + WPB - 1) / WPB;
+    constexpr int NI = 5 + XI;                   // DMA instructions per wave per slot (W: 3 x 1 KiB + 2 x 256 B)
+    static_assert(NI * (D - 2) < 64, "vmcnt range");
+    __shared__ __attribute__((aligned(1024))) char lds[D * SLOT + LDS_XTRA];
+    float* const s_ss = reinterpret_cast<float*>(lds + D * SLOT + 1024);
+
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int n0 = blockIdx.x * R;
+    const int ks = blockIdx.y * kper;
+    const int nkb = kper / KBLK;
+
+    // this wave's tiles: group n0 / 16 + w, k blocks ks / 128 ...
+    const unsigned char* const wsrc = W + ((size_t)(n0 / 16 + w) * (K / KBLK) + ks / KBLK) * P14_TILE;
+    const int prow = lane >> 3, pslot = lane & 7;
+    const bf16* xsrc[XI];
+    int xdst[XI];
+#pragma unroll
+    for (int i = 0; i < XI; ++i) {
+        const int q = w + WPB * i;  // x piece index; >= XP -> dummy
+        const int qq = q < XP ? q : 0;
+        const int row = 8 * (qq >> 1) + prow;
+        xsrc[i] = x + (size_t)min(row, M - 1) * ldx + ks + 8 * (8 * (qq & 1) + (pslot ^ prow));
+        xdst[i] = q < XP ? WBYTES + q * 1024 : -1;
+    }
+#define ISSUE14(slot, kb)                                                                            \
+    {                                                                                                \
+        char* base = lds + (slot) * SLOT;                                                            \
+        char* wb = base + w * P14_TILE;                                                              \
+        const unsigned char* ws = wsrc + (size_t)(kb) * P14_TILE;                                    \
+        glds16<2>(ws + 16 * lane, wb);                                                               \
+        glds16<2>(ws + 1024 + 16 * lane, wb + 1024);                                                 \
+        glds16<2>(ws + P14_NIB + 16 * lane, wb + P14_NIB);                                           \
+        glds4<2>(ws + P14_TWO + 4 * lane, wb + P14_TWO);                                             \
+        glds4<2>(ws + P14_TWO + 256 + 4 * lane, wb + P14_TWO + 256);                                 \
+        _Pragma("unroll") for (int i = 0; i < XI; ++i)                                               \
+            glds16(xsrc[i] + (kb) * KBLK, xdst[i] >= 0 ? base + xdst[i] : lds + D * SLOT);           \
+    }
+
+    f32x4 acc[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+#pragma unroll
+    for (int s = 0; s < D - 1; ++s) ISSUE14(s, min(s, nkb - 1));
+
+    const uint32_t base4 = (uint32_t)(base7 - 1) * 0x01010101u;  // added to every non-zero code
+    const int r = lane & 15, g = lane >> 4;
+    for (int j = 0; j < nkb; ++j) {
+        if (j + D - 2 < nkb) wait_vmcnt<NI * (D - 2)>();
+        else wait_vmcnt<0>();
+        raw_barrier();
+        if (j + D - 1 < nkb) ISSUE14((j + D - 1) % D, j + D - 1);
+        const char* wl = lds + (j % D) * SLOT + w * P14_TILE;
+        const char* xl = lds + (j % D) * SLOT + WBYTES;
+        const u32x4 lo0 = *reinterpret_cast<const u32x4*>(wl + 16 * lane);
+        const u32x4 lo1 = *reinterpret_cast<const u32x4*>(wl + 1024 + 16 * lane);
+        const u32x4 nb = *reinterpret_cast<const u32x4*>(wl + P14_NIB + 16 * lane);
+        const u32x2 s2 = *reinterpret_cast<const u32x2*>(wl + P14_TWO + 8 * lane);
+        bf16x8 av[4];
+        av[0] = p14_frag<0>(lo0[0], lo0[1], nb[0], s2.x, base4);
+        av[1] = p14_frag<1>(lo0[2], lo0[3], nb[1], s2.x, base4);
+        av[2] = p14_frag<0>(lo1[0], lo1[1], nb[2], s2.y, base4);
+        av[3] = p14_frag<1>(lo1[2], lo1[3], nb[3], s2.y, base4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                const u32x4 bv = *reinterpret_cast<const u32x4*>(xl + img_off(16 * m + r, 4 * i + g));
+                acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[i], __builtin_bit_cast(bf16x8, bv), acc[m], 0, 0, 0);
+            }
+        }
+    }
+#undef ISSUE14
+
+    stream_epilogue<MT, EPI, WPB>(acc, lds, s_ss, n0, M, out, ldo, parts, counters, e);
+}
+
+// Same contract as mrsum_stream_gemm at M <= 64 and without a TP push (``ar`` must be null), with W the p14
+// tiles of a packable [N, K] bf16 matrix (mrsum_p14_pack) and base7 its window base.  Bit-identical to
+// mrsum_stream_gemm on the unpacked matrix with the same (M, splits, wpb).
+MRSUM_API int mrsum_stream_p14(const void* x, int ldx, const void* W, int base7, int N, int K, int M, void* out,
+                               int ldo, int epi, int splits, int wpb, void* parts, int* counters, const float* ssq,
+                               int ssq_tiles, float eps, void* resid, int ldr, float* ssp, void* ar, hipStream_t s) {
+    if (M <= 0) return 0;
+    if (wpb < 4 || wpb > 8 || M > 64 || K % KBLK || N % (16 * wpb) || splits < 1 || (K / KBLK) % splits ||
+        epi < EPI_BF16 || epi > EPI_RESID_SPLIT || base7 < 1 || base7 > 97 || ar)
+        return (int)hipErrorInvalidValue;
+    const bool split_epi = epi == EPI_SWIGLU_SPLIT || epi == EPI_RESID_SPLIT;
+    if (epi != EPI_F32_PARTIAL && !split_epi && splits != 1) return (int)hipErrorInvalidValue;
+    if (split_epi && (!parts || !counters)) return (int)hipErrorInvalidValue;
+    if (epi == EPI_RESID_SPLIT && (!resid || !ssp || ldr % 4)) return (int)hipErrorInvalidValue;
+    if (ssq && (ssq_tiles <= 0 || ssq_tiles % (4 * SS_PARTS))) return (int)hipErrorInvalidValue;
+    NormArgs e;
+    e.ssq = ssq; e.ssq_tiles = ssq_tiles; e.inv_k = 1.f / (float)K; e.eps = eps;
+    e.resid = (bf16*)resid; e.ldr = ldr; e.ssp = ssp; e.slab_m = 0;
+    e.tp = mrsum_ar::tp_push_of(nullptr);
+    const int kper = K / splits;
+    const int mt = (M + 15) / 16;
+    dim3 grid(N / (16 * wpb), splits), block(64 * wpb);
+    auto X = (const bf16*)x;
+    auto Wp = (const unsigned char*)W;
+    auto P = (float*)parts;
+#define L14(MT_, EPI_, WPB_) \
+    stream_p14_kernel<MT_, EPI_, WPB_><<<grid, block, 0, s>>>(X, ldx, Wp, base7, K, M, out, ldo, kper, P, counters, e)
+#define BY_WPB14(MT_, EPI_)                         \
+    switch (wpb) {                                  \
+        case 4: L14(MT_, EPI_, 4); break;           \
+        case 5: L14(MT_, EPI_, 5); break;           \
+        case 6: L14(MT_, EPI_, 6); break;           \
+        case 7: L14(MT_, EPI_, 7); break;           \
+        default: L14(MT_, EPI_, 8); break;          \
+    }
+#define BY_EPI14(MT_)                                                      \
+    if (epi == EPI_BF16) { BY_WPB14(MT_, EPI_BF16) }                       \
+    else if (epi == EPI_F32_PARTIAL) { BY_WPB14(MT_, EPI_F32_PARTIAL) }    \
+    else if (epi == EPI_SWIGLU) { BY_WPB14(MT_, EPI_SWIGLU) }              \
+    else if (epi == EPI_SWIGLU_SPLIT) { BY_WPB14(MT_, EPI_SWIGLU_SPLIT) }  \
+    else { BY_WPB14(MT_, EPI_RESID_SPLIT) }
+    switch (mt) {
+        case 1: BY_EPI14(1); break;
+        case 2: BY_EPI14(2); break;
+        case 3: BY_EPI14(3); break;
+        default: BY_EPI14(4); break;
+    }
+#undef BY_EPI14
+#undef BY_WPB14
+#undef L14
+    return (int)hipGetLastError();
+}
+
+// p14 packer: one pass for the matrix's largest e7, one that writes the tiles and counts the elements
+// whose e7 falls outside the window (their codes are meaningless: the caller keeps the bf16 kernel).
+namespace {
+__global__ __launch_bounds__(256) void p14_max_kernel(const uint4* __restrict__ W, size_t n16, int* __restrict__ stats) {
+    uint32_t m = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x) {
+        const uint4 v = W[i];
+        const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) m = max(m, max((d[c] >> 8) & 0x7fu, (d[c] >> 24) & 0x7fu));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+    if ((threadIdx.x & 63) == 0) atomicMax(stats, (int)m);
+}
+
+// one wave per tile; lane l = 16 g + r packs its 32 weights (see the format above)
+__global__ __launch_bounds__(64) void p14_pack_kernel(const bf16* __restrict__ W, int K, unsigned char* __restrict__ P,
+                                                      int* __restrict__ stats) {
+    const int lane = threadIdx.x, r = lane & 15, g = lane >> 4;
+    const int nkb = K / KBLK;
+    const size_t tile = blockIdx.x;
+    const int G = (int)(tile / nkb), kb = (int)(tile % nkb);
+    const int base7 = max(stats[0] - 30, 1);
+    const uint4* src = reinterpret_cast<const uint4*>(W + (size_t)(16 * G + r) * K + (size_t)kb * KBLK + 8 * g);
+    uint32_t lo[8], nb[4], s2[2] = {0u, 0u};
+    int bad = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint4 v = src[4 * i];  // 32 i + 8 g: steps are 32 weights = 4 uint4 apart
+        const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+        lo[2 * i] = lo[2 * i + 1] = nb[i] = 0u;
+#pragma unroll
+        for (int el = 0; el < 8; ++el) {
+            const uint32_t wv = (d[el >> 1] >> (16 * (el & 1))) & 0xffffu;
+            const int e7 = (wv >> 8) & 0x7f, c = e7 ? e7 - base7 + 1 : 0;
+            bad += e7 && (c < 1 || c > 31);
+            const uint32_t c5 = (uint32_t)c & 31u, sg = wv >> 15;
+            const int b = el & 3, q = 2 * (i & 1) + (el >> 2);
+            lo[2 * i + (el >> 2)] |= (wv & 0xffu) << (8 * b);
+            nb[i] |= (c5 & 15u) << (8 * b + 4 * (el >> 2));
+            s2[i >> 1] |= (c5 >> 4) << (8 * b + 4 - q) | sg << (8 * b + 7 - (q == 3 ? 7 : q));
+        }
+    }
+    unsigned char* t = P + tile * P14_TILE;
+    *reinterpret_cast<uint4*>(t + 16 * lane) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+    *reinterpret_cast<uint4*>(t + 1024 + 16 * lane) = make_uint4(lo[4], lo[5], lo[6], lo[7]);
+    *reinterpret_cast<uint4*>(t + P14_NIB + 16 * lane) = make_uint4(nb[0], nb[1], nb[2], nb[3]);
+    *reinterpret_cast<uint2*>(t + P14_TWO + 8 * lane) = make_uint2(s2[0], s2[1]);
+    if (bad) atomicAdd(stats + 1, bad);
+}
+}  // namespace
+
+// W bf16 [N, K] contiguous (N % 16 == 0, K % 128 == 0) -> packed N * K * 7 / 4 bytes; stats int[2] =
+// {largest e7, out-of-window elements} (base7 = max(stats[0] - 30, 1); packable iff stats[1] == 0).
+MRSUM_API int mrsum_p14_pack(const void* W, int N, int K, void* packed, int* stats, hipStream_t s) {
+    if (N <= 0 || K <= 0 || N % 16 || K % KBLK || !W || !packed || !stats) return (int)hipErrorInvalidValue;
+    hipError_t rc = hipMemsetAsync(stats, 0, 2 * sizeof(int), s);
+    if (rc != hipSuccess) return (int)rc;
+    const size_t n16 = (size_t)N * K / 8;
+    const int blocks = (int)((n16 + 255) / 256 < 4096 ? (n16 + 255) / 256 : 4096);
+    p14_max_kernel<<<blocks, 256, 0, s>>>((const uint4*)W, n16, stats);
+    p14_pack_kernel<<<(unsigned)((size_t)(N / 16) * (K / KBLK)), 64, 0, s>>>((const bf16*)W, K, (unsigned char*)packed,
+                                                                              stats);
+    return (int)hipGetLastError();
+}

@@ -47,6 +47,9 @@ _SIGS = {
                           _vp, _c_int, _c_float, _vp, _c_int, _vp, _c_int, _vp, _vp],
     "mrsum_stream_fp8": [_vp, _c_int, _vp, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp,
                          _vp, _c_int, _c_float, _vp, _c_int, _vp, _vp, _vp],
+    "mrsum_stream_p14": [_vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp,
+                         _vp, _vp, _c_int, _c_float, _vp, _c_int, _vp, _vp, _vp],
+    "mrsum_p14_pack": [_vp, _c_int, _c_int, _vp, _vp, _vp],
     "mrsum_skinny_fp8": [_vp, _c_int, _vp, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp,
                          _c_int, _c_float, _vp, _c_int, _vp, _vp, _c_int, _vp],
     "mrsum_skinny_fp8_resid_capacity": [],
@@ -1030,9 +1033,100 @@ def _stream_launch(x, w, out, epi, splits, ldo, wpb, parts, counters, norm, resi
         _req(ssp.shape[1] == N // (16 * wpb), "stream_gemm: ssp tiles")
     sq, tiles, eps = _norm_args(x, norm)
     rp, ldr, sp = _resid_args(x, N, epi, resid, ssp)
+    pw = p14_lookup(w) if _P14 else None
+    if pw is not None and M <= SKINNY_MAX_M and not slab_m and ar is None and p14_takes(pw.role, M):
+        STATS["stream_p14"] += 1
+        _check(_fn("mrsum_stream_p14")(_p(x), x.stride(0), _p(pw.packed), pw.base7, N, K, M, _p(out), ldo, epi, splits,
+                                       wpb, _p(parts), _p(counters), sq, tiles, eps, rp, ldr, sp, None, _stream()),
+               "stream_p14")
+        return out
+    STATS["stream_bf16"] += 1
     _check(_fn("mrsum_stream_gemm")(_p(x), x.stride(0), _p(w), N, K, M, _p(out), ldo, epi, splits, wpb, _p(parts),
                                     _p(counters), sq, tiles, eps, rp, ldr, sp, slab_m, ar, _stream()), "stream_gemm")
     return out
+
+
+# ------------------------------------------------------------------ p14: lossless 14-bit packed bf16 decode weights
+# (stream_gemm.hip "p14"; ops/reference.py p14_pack_ref is the bit-level reference of the format)
+P14_ROLES = ("qkv", "o", "gate_up", "down", "lm_head")
+# (role, row bucket) pairs whose stream GEMM reads the packed form (MRSUM_P14=0: none), adopted where the
+# kernel ran faster inside whole headline steps (docs/decode_latency.md "p14", profiles/
+# p14_e2e_10h_kernel_summary.txt, us per dispatch bf16 -> p14): gate_up 42.0 -> 35.7 at 1 and at 39 rows, LM head
+# 187.2 -> 163.9 at one row, down 23.1 -> 22.9 at one row.  Not adopted: qkv (10.8 -> 11.8 at one row, 12.3 ->
+# 12.9 at 39), o / down at 39 rows (15.5 -> 16.6), the LM head at 39 rows (187.3 -> 194.2) -- split-K grids of
+# 8-28 k blocks per workgroup, where the deeper ring's ramp and the decode outweigh the bytes.  Bucket = 1, 16
+# or 64 rows (one-row-tile kernels serve the first two).
+_P14_PLAN = {("gate_up", 1), ("gate_up", 16), ("gate_up", 64), ("lm_head", 1), ("lm_head", 16),
+             ("down", 1), ("down", 16)}
+_P14 = {}  # (data_ptr, N, K) of a registered bf16 weight -> PackedWeight
+
+
+class PackedWeight:
+    """A bf16 decode weight [N, K] with its p14 tiles: ``w`` (kept: prefill and every kernel but the stream GEMM
+    read it, and it is the fallback), ``packed`` uint8 [N * K * 7 / 4], ``base7`` and the ``packable`` verdict
+    (every exponent inside the 64-binade window; an unpackable weight has no tiles)."""
+
+    def __init__(self, w: torch.Tensor, packed: Optional[torch.Tensor], base7: int, packable: bool, role: str):
+        self.w, self.packed, self.base7, self.packable, self.role = w, packed, base7, packable, role
+
+    def nbytes(self) -> int:
+        return self.packed.numel() if self.packed is not None else 0
+
+
+def p14_enabled() -> bool:
+    """MRSUM_P14=0 turns the packed path off (default: on); read per call, so one process can compare both."""
+    return os.environ.get("MRSUM_P14", P14_DEFAULT) == "1"
+
+
+P14_DEFAULT = "1"
+
+
+def p14_bucket(M: int) -> int:
+    return 1 if M == 1 else 16 if M <= 16 else 64
+
+
+def p14_role_used(role: str) -> bool:
+    """Whether any row bucket of ``role`` reads the packed form (else packing it only costs memory)."""
+    return any(r == role for r, _ in _P14_PLAN)
+
+
+def p14_takes(role: str, M: int) -> bool:
+    return p14_enabled() and (role, p14_bucket(M)) in _P14_PLAN
+
+
+def p14_pack(w: torch.Tensor):
+    """(tiles uint8 [N * K * 7 / 4], base7, out-of-window element count) of a bf16 [N, K] matrix, packed on the
+    GPU (synchronises: a load-time step)."""
+    _bf16_cuda(w)
+    _req(w.dim() == 2 and w.is_contiguous() and w.shape[0] % 16 == 0 and w.shape[1] % 128 == 0,
+         "p14_pack: expected a contiguous bf16 [16 n, 128 k] matrix")
+    N, K = w.shape
+    packed = torch.empty(N * K // 4 * 7, dtype=torch.uint8, device=w.device)
+    stats = torch.zeros(2, dtype=torch.int32, device=w.device)
+    _check(_fn("mrsum_p14_pack")(_p(w), N, K, _p(packed), _p(stats), _stream()), "p14_pack")
+    mx, bad = (int(v) for v in stats.tolist())
+    return packed, max(mx - 30, 1), bad
+
+
+def p14_attach(w: torch.Tensor, role: str) -> PackedWeight:
+    """Pack ``w`` and register it: stream GEMMs called with this very tensor read the tiles where the plan says
+    so.  An unpackable matrix keeps the bf16 kernel."""
+    _req(role in P14_ROLES, "p14_attach: unknown role %r" % (role,))
+    packed, base7, bad = p14_pack(w)
+    if bad:
+        print("p14: %s weight %s has %d elements outside the exponent window: bf16 kernel kept"
+              % (role, tuple(w.shape), bad))
+        return PackedWeight(w, None, base7, False, role)
+    pw = _P14[(w.data_ptr(), w.shape[0], w.shape[1])] = PackedWeight(w, packed, base7, True, role)
+    return pw
+
+
+def p14_detach(w: torch.Tensor) -> None:
+    _P14.pop((w.data_ptr(), w.shape[0], w.shape[1]), None)
+
+
+def p14_lookup(w: torch.Tensor) -> Optional[PackedWeight]:
+    return _P14.get((w.data_ptr(), w.shape[0], w.shape[1]))
 
 
 def linear_takes_norm(M: int, N: int, K: int) -> bool:
@@ -1236,7 +1330,9 @@ def add_rmsnorm_parts(parts: torch.Tensor, residual: torch.Tensor, w: torch.Tens
 # Streaming floor (probe): qkv 9.5, o 7.6, down 20.1, gate_up 39.1.
 # Plan = ("stream", wpb, S) | ("skinny", nt, S) | ("lds", S) | ("gemm",) (the 256 x 256-tile kernel)
 N_CU = 256
-STATS = {"tp_push": 0}  # host-side launch counts of selected paths (tests check which path ran)
+# host-side launch counts of selected paths (tests check which path ran); stream_p14 / stream_bf16: which form
+# of the weight a stream GEMM launch read
+STATS = {"tp_push": 0, "stream_p14": 0, "stream_bf16": 0}
 
 
 def stream_config(N: int, K: int, swiglu: bool = False, splits: Optional[int] = None, max_splits: int = 16):

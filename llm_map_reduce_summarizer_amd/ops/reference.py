@@ -219,6 +219,80 @@ def _w(w):
     return w.dequant(torch.bfloat16) if isinstance(w, Fp8Weight) else w
 
 
+# ------------------------------------------------------------------ p14: lossless 14-bit bf16 weights
+# Bit-level reference of the format of csrc/kernels/stream_gemm.hip ("p14"): lo = w & 0xff verbatim,
+# hi = w >> 8 as the 6-bit code (sign << 5) | c5 with e7 = hi & 0x7f: c5 = 0 for e7 = 0 (zeros, subnormals,
+# the smallest normals), else c5 = e7 - base7 + 1 in 1..31, base7 = max(max e7 - 30, 1).
+# One 3584-byte tile per (16-row group, 128-wide k block); lane l = 16 g + r of the tile owns
+# W[16 G + r][128 kb + 32 i + 8 g + e] (i < 4 MFMA steps, e < 8).
+P14_TILE = 3584
+P14_WINDOW = 31  # e7 values of the window [base7, base7 + 30]; e7 = 0 has a code of its own
+_P14_SIGN_SHIFT = (0, 1, 2, 7)  # sign bit of byte b at 8 b + 7 - shift[q], q = 2 (i & 1) + (e >> 2)
+
+
+def p14_bits(w: torch.Tensor) -> torch.Tensor:
+    """The 16 bits of every bf16 element as int64."""
+    return w.contiguous().view(torch.int16).to(torch.int64) & 0xffff
+
+
+def p14_base7(w: torch.Tensor) -> int:
+    return max(int(((p14_bits(w) >> 8) & 0x7f).max()) - (P14_WINDOW - 1), 1)
+
+
+def _p14_lanes(u: torch.Tensor) -> torch.Tensor:
+    """[N, K] -> [tiles, 64 lanes, 4 steps, 8] in the tile order (group-major, k blocks consecutive)."""
+    N, K = u.shape
+    t = u.reshape(N // 16, 16, K // 128, 4, 4, 8)  # G, r, kb, i, g, e
+    return t.permute(0, 2, 4, 1, 3, 5).reshape(-1, 64, 4, 8)
+
+
+def p14_pack_ref(w: torch.Tensor):
+    """bf16 [N, K] (N % 16 == 0, K % 128 == 0) -> (uint8 [N * K * 7 / 4] tiles, base7, out-of-window count).
+    The matrix is packable iff the count is zero (an out-of-window element's code keeps only its low 5 bits)."""
+    N, K = w.shape
+    assert w.dtype == torch.bfloat16 and N % 16 == 0 and K % 128 == 0
+    u = _p14_lanes(p14_bits(w))
+    base7 = p14_base7(w)
+    e7 = (u >> 8) & 0x7f
+    c = torch.where(e7 == 0, e7, e7 - base7 + 1)
+    bad = int(((e7 != 0) & ((c < 1) | (c > P14_WINDOW))).sum())
+    c5, sg = c & 31, u >> 15
+    T = u.shape[0]
+    lo = (u & 0xff).reshape(T, 64, 2, 16).permute(0, 2, 1, 3).reshape(T, 2048)
+    q4 = c5 & 15
+    nib = (q4[..., :4] | q4[..., 4:] << 4).reshape(T, 1024)
+    two = torch.zeros(T, 64, 2, dtype=torch.int64, device=u.device)
+    for i in range(4):
+        for e in range(8):
+            b, q = e & 3, 2 * (i & 1) + (e >> 2)
+            two[:, :, i >> 1] |= (c5[:, :, i, e] >> 4) << (8 * b + 4 - q)
+            two[:, :, i >> 1] |= sg[:, :, i, e] << (8 * b + 7 - _P14_SIGN_SHIFT[q])
+    two = torch.stack([(two >> (8 * k)) & 0xff for k in range(4)], dim=-1).reshape(T, 512)
+    return torch.cat([lo, nib, two], dim=1).to(torch.uint8).reshape(-1), base7, bad
+
+
+def p14_unpack_ref(packed: torch.Tensor, base7: int, N: int, K: int) -> torch.Tensor:
+    """Inverse of p14_pack_ref for a packable matrix: the original bf16 [N, K], bit for bit."""
+    t = packed.reshape(-1, P14_TILE).to(torch.int64)
+    T = t.shape[0]
+    lo = t[:, :2048].reshape(T, 2, 64, 2, 8).permute(0, 2, 1, 3, 4).reshape(T, 64, 4, 8)
+    nb = t[:, 2048:3072].reshape(T, 64, 4, 4)
+    q4 = torch.cat([nb & 15, nb >> 4], dim=-1)
+    tb = t[:, 3072:].reshape(T, 64, 2, 4)
+    two = sum(tb[..., k] << (8 * k) for k in range(4))
+    hi = torch.zeros_like(lo)
+    for i in range(4):
+        for e in range(8):
+            b, q = e & 3, 2 * (i & 1) + (e >> 2)
+            s = two[:, :, i >> 1]
+            c5 = q4[:, :, i, e] | ((s >> (8 * b + 4 - q)) & 1) << 4
+            e7 = torch.where(c5 == 0, c5, c5 + base7 - 1)
+            hi[:, :, i, e] = ((s >> (8 * b + 7 - _P14_SIGN_SHIFT[q])) & 1) << 7 | e7
+    u = (hi << 8 | lo).reshape(N // 16, K // 128, 4, 16, 4, 8).permute(0, 3, 1, 4, 2, 5).reshape(N, K)
+    u = torch.where(u >= 0x8000, u - 0x10000, u)
+    return u.to(torch.int16).view(torch.bfloat16)
+
+
 def linear(x: torch.Tensor, w) -> torch.Tensor:
     if isinstance(w, Fp8Weight):
         return (x.float() @ w.dequant().t()).to(x.dtype)
