@@ -493,6 +493,260 @@ __global__ void sample_finish_stops_kernel(unsigned long long* __restrict__ resu
     finish_row<true>(result, next_ids, positions, gen_count, max_new, out_tokens, out_stride, done, eos, stop_ids, B);
 }
 
+// ------------------------------------------------------------------ token log-probabilities
+// logprobs: the log-softmax of the rows the sampler is about to see (after constrain / penalize, at T = 1, before
+//          the filter) and their top lists (ops/reference.py token_logprobs is the definition).  The kernels
+//          only read the logits.
+//          logprobs_seg   grid (LP_SEGS, B): workgroup (s, b) scans segment s of row b (16-B loads, scalar tail)
+//                         once per quantity -- its largest key, its sum exp(x - segment max), then, every wave
+//                         on its own columns and without a barrier, one pass per top entry (the largest key
+//                         below the previous one: the keys of a row are distinct, (order key of the value, -0
+//                         as +0) << 32 | ~token, so ties go to the lower id); wave 0 picks the segment's n
+//                         largest of the four lists.  A thread keeps the keys of its first 16 columns in
+//                         registers -- a whole segment up to V = 131072, so a Llama-3 row is read once --
+//                         and reads the columns past them again in every pass (this CU's L1 / the L2), so no
+//                         V is too large.  It stores (max, sum) and its lp_n[b] keys with plain stores into
+//                         the row's workspace.
+//          logprobs_merge one wave per row, a second kernel: the kernel boundary makes the segments' plain
+//                         stores visible, where a last-arriver tail would need a ticket atomic, its reset and
+//                         fences for a merge this small.  It folds the segments IN SEGMENT ORDER -- M = max,
+//                         S = sum_s sum_s * exp(max_s - M), one thread adding the 32 terms one after the other
+//                         -- picks the top lp_n[b] of the <= 32 * lp_n[b] keys and writes them with
+//                         lp = (v - M) - log S straight into the row's record of step gen_count[b], read
+//                         BEFORE the finish advances it.  lse_m / lse_logS / lp_slot hand M, log S and that
+//                         step to the pick kernel; lp_slot[b] = -1 says "no record this step".
+//          logprobs_pick  after the finish (whichever ran): one thread per row with lp_slot[b] >= 0 reads the
+//                         token the finish appended and its logit from the still unmodified row and stores
+//                         (v - M) - log S, the very operations of the top list: bit-equal to its entry there.
+//          Rows with lp_n[b] < 0 (off), done rows and rows whose step is past the record width write no
+//          record; their lp_slot is -1, so the pick skips them (a done row keeps running in a captured graph:
+//          a stale slot would rewrite its last record from the wrong logits).  No global atomics, no float
+//          atomics, nothing depends on B or on the row's index: the same row gives the same bits anywhere.
+constexpr int LP_SEGS = 32;
+constexpr int LP_TOP = 20;  // OpenAI's top_logprobs limit (ops.hip.LOGPROBS_TOP)
+constexpr int LP_THREADS = 256;
+constexpr int LP_MERGE_KEYS = LP_SEGS * LP_TOP / 64;  // keys per lane of the merging wave
+constexpr int LP_CACHE = 2;  // 16-B loads of a thread whose keys stay in registers (32 VGPRs)
+constexpr int LP_WAVE_KEYS = ((LP_THREADS / 64) * LP_TOP + 63) / 64;  // ... and of a segment's wave 0
+
+__device__ __forceinline__ unsigned long long lp_key(float v, int tok) {
+    unsigned int bits = __float_as_uint(v);
+    if (bits == 0x80000000u) bits = 0u;  // -0 -> +0: compared as numbers
+    const unsigned int o = (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
+    return ((unsigned long long)o << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned int)tok);
+}
+
+__device__ __forceinline__ float lp_key_value(unsigned long long k) {
+    const unsigned int o = (unsigned int)(k >> 32);
+    return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
+}
+
+__device__ __forceinline__ unsigned long long lp_wave_max(unsigned long long k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(k, o, 64);
+        k = other > k ? other : k;
+    }
+    return k;
+}
+
+__device__ __forceinline__ unsigned long long lp_block_max(unsigned long long k, unsigned long long* red) {
+    k = lp_wave_max(k);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = k;
+    __syncthreads();
+    unsigned long long m = red[0];
+    for (int i = 1; i < LP_THREADS / 64; ++i) m = red[i] > m ? red[i] : m;
+    __syncthreads();
+    return m;
+}
+
+// f(value, column) over this thread's share of the columns [c0, c1) of a row (c0 a multiple of 8)
+template <class F>
+__device__ __forceinline__ void lp_scan(const bf16* __restrict__ row, int c0, int c1, F f) {
+    for (int c = c0 + threadIdx.x * 8; c < c1; c += LP_THREADS * 8) {
+        float x[8];
+        if (c + 8 <= c1) {
+            unpack8(*reinterpret_cast<const uint4*>(row + c), x);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) x[j] = c + j < c1 ? (float)row[c + j] : -INFINITY;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (c + j < c1) f(x[j], c + j);
+    }
+}
+
+__device__ __forceinline__ bool lp_row_live(int n, int g, int done, int cap) { return n >= 0 && !done && g < cap; }
+
+__global__ __launch_bounds__(LP_THREADS) void logprobs_seg_kernel(const bf16* __restrict__ logits, int ld, int V,
+                                                                  const int* __restrict__ lp_n,
+                                                                  const int* __restrict__ gen_count,
+                                                                  const int* __restrict__ done, int cap, int seg_len,
+                                                                  float2* __restrict__ seg_ms,
+                                                                  unsigned long long* __restrict__ seg_keys) {
+    __shared__ unsigned long long red[LP_THREADS / 64];
+    __shared__ float fred[LP_THREADS / 64];
+    __shared__ unsigned long long s_keys[LP_THREADS / 64][LP_TOP];
+    const int b = blockIdx.y;
+    const int n = min(lp_n[b], LP_TOP);
+    if (!lp_row_live(n, gen_count[b], done[b], cap)) return;  // block-uniform
+    const int c0 = min(V, (int)blockIdx.x * seg_len);  // (a short row leaves its last segments empty)
+    const int c1 = min(V, c0 + seg_len);
+    const bf16* row = logits + (size_t)b * ld;
+    // the keys of this thread's first LP_CACHE x 8 columns stay in registers (a whole segment up to V = 32 *
+    // LP_CACHE * 2048 = 131072); the columns past them are read again in every pass, from this CU's L1 / the L2
+    unsigned long long kc[LP_CACHE * 8];  // 0 = no column: no key is 0, a token id is below 2^31
+#pragma unroll
+    for (int i = 0; i < LP_CACHE; ++i) {
+        const int c = c0 + (i * LP_THREADS + (int)threadIdx.x) * 8;
+        float x[8];
+        if (c + 8 <= c1) {
+            unpack8(*reinterpret_cast<const uint4*>(row + c), x);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) x[j] = c + j < c1 ? (float)row[c + j] : -INFINITY;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) kc[i * 8 + j] = c + j < c1 ? lp_key(x[j], c + j) : 0ULL;
+    }
+    const int cr = min(c1, c0 + LP_CACHE * LP_THREADS * 8);  // [cr, c1): the columns not cached
+    unsigned long long best = 0ULL;
+#pragma unroll
+    for (int i = 0; i < LP_CACHE * 8; ++i) best = kc[i] > best ? kc[i] : best;
+    lp_scan(row, cr, c1, [&](float v, int t) {
+        const unsigned long long k = lp_key(v, t);
+        best = k > best ? k : best;
+    });
+    best = lp_block_max(best, red);
+    const float m = best ? lp_key_value(best) : -INFINITY;
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < LP_CACHE * 8; ++i) {
+        const float v = lp_key_value(kc[i]);  // (-0 comes back as +0: the same exp)
+        s += (kc[i] && v > -INFINITY) ? __expf(v - m) : 0.f;
+    }
+    lp_scan(row, cr, c1, [&](float v, int) { s += v > -INFINITY ? __expf(v - m) : 0.f; });
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) fred[threadIdx.x >> 6] = s;
+    __syncthreads();
+    const size_t seg = (size_t)b * LP_SEGS + blockIdx.x;
+    if (threadIdx.x == 0) {
+        float t = fred[0];
+        for (int i = 1; i < LP_THREADS / 64; ++i) t += fred[i];
+        seg_ms[seg] = make_float2(m, t);
+    }
+    if (n == 0) return;  // block-uniform
+    // the top n: every wave lists the n largest keys of its own columns (one pass over its keys and one wave
+    // reduction per entry, no barrier), then wave 0 picks the n largest of the LP_THREADS / 64 lists
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    unsigned long long prev = ~0ULL;
+    for (int r = 0; r < n; ++r) {  // wave-uniform
+        unsigned long long next = 0ULL;
+        if (prev) {
+#pragma unroll
+            for (int i = 0; i < LP_CACHE * 8; ++i) next = (kc[i] < prev && kc[i] > next) ? kc[i] : next;
+            lp_scan(row, cr, c1, [&](float v, int t) {
+                const unsigned long long k = lp_key(v, t);
+                next = (k < prev && k > next) ? k : next;
+            });
+            next = lp_wave_max(next);
+        }
+        if (lane == 0) s_keys[wid][r] = next;  // 0 once the wave's columns are exhausted
+        prev = next;
+    }
+    __syncthreads();
+    if (wid != 0) return;
+    unsigned long long k[LP_WAVE_KEYS];
+#pragma unroll
+    for (int j = 0; j < LP_WAVE_KEYS; ++j) {
+        const int i = lane + 64 * j;  // list i / LP_TOP, entry i % LP_TOP
+        k[j] = (i < (LP_THREADS / 64) * LP_TOP && i % LP_TOP < n) ? s_keys[i / LP_TOP][i % LP_TOP] : 0ULL;
+    }
+    unsigned long long* keys = seg_keys + seg * LP_TOP;
+    prev = ~0ULL;
+    for (int r = 0; r < n; ++r) {
+        unsigned long long next = 0ULL;
+#pragma unroll
+        for (int j = 0; j < LP_WAVE_KEYS; ++j) next = (k[j] < prev && k[j] > next) ? k[j] : next;
+        next = lp_wave_max(next);
+        if (lane == 0) keys[r] = next;  // 0 once the segment is exhausted
+        prev = next;
+    }
+}
+
+__global__ __launch_bounds__(64) void logprobs_merge_kernel(const int* __restrict__ lp_n,
+                                                            const int* __restrict__ gen_count,
+                                                            const int* __restrict__ done, int cap,
+                                                            const float2* __restrict__ seg_ms,
+                                                            const unsigned long long* __restrict__ seg_keys,
+                                                            float* __restrict__ lse_m, float* __restrict__ lse_logS,
+                                                            int* __restrict__ lp_slot, int* __restrict__ out_top_tok,
+                                                            float* __restrict__ out_top_lp) {
+    __shared__ float s_term[LP_SEGS];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int n = min(lp_n[b], LP_TOP);
+    const int g = gen_count[b];
+    if (!lp_row_live(n, g, done[b], cap)) {  // block-uniform
+        if (lane == 0) lp_slot[b] = -1;
+        return;
+    }
+    const float2 ms = lane < LP_SEGS ? seg_ms[(size_t)b * LP_SEGS + lane] : make_float2(-INFINITY, 0.f);
+    const float M = wave_max(ms.x);
+    if (lane < LP_SEGS) s_term[lane] = ms.x > -INFINITY ? ms.y * __expf(ms.x - M) : 0.f;
+    __syncthreads();
+    float S = 0.f;
+    for (int i = 0; i < LP_SEGS; ++i) S += s_term[i];  // segment order, the same on every lane
+    const float logS = __logf(S);
+    unsigned long long k[LP_MERGE_KEYS];
+    const unsigned long long* keys = seg_keys + (size_t)b * (LP_SEGS * LP_TOP);
+#pragma unroll
+    for (int j = 0; j < LP_MERGE_KEYS; ++j) {
+        const int i = lane + 64 * j;
+        k[j] = i % LP_TOP < n ? keys[i] : 0ULL;  // a segment wrote its first n slots only
+    }
+    unsigned long long prev = ~0ULL;
+    int my_tok = -1;
+    float my_lp = -INFINITY;
+    for (int r = 0; r < n; ++r) {
+        unsigned long long best = 0ULL;
+#pragma unroll
+        for (int j = 0; j < LP_MERGE_KEYS; ++j) best = (k[j] < prev && k[j] > best) ? k[j] : best;
+        best = lp_wave_max(best);
+        if (lane == r && best) {  // (fewer than n tokens in the row: the other entries stay -1 / -inf)
+            my_tok = (int)(0xFFFFFFFFu - (unsigned int)(best & 0xFFFFFFFFULL));
+            my_lp = (lp_key_value(best) - M) - logS;
+        }
+        prev = best;
+    }
+    if (lane < n) {
+        const size_t at = ((size_t)b * cap + g) * LP_TOP + lane;
+        out_top_tok[at] = my_tok;
+        out_top_lp[at] = my_lp;
+    }
+    if (lane == 0) {
+        lse_m[b] = M;
+        lse_logS[b] = logS;
+        lp_slot[b] = g;
+    }
+}
+
+__global__ void logprobs_pick_kernel(const bf16* __restrict__ logits, int ld, int V,
+                                     const int* __restrict__ out_tokens, int out_stride,
+                                     const int* __restrict__ lp_slot, const float* __restrict__ lse_m,
+                                     const float* __restrict__ lse_logS, float* __restrict__ out_logprobs, int cap,
+                                     int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int slot = lp_slot[b];
+    if (slot < 0 || slot >= cap || slot >= out_stride) return;
+    const int tok = out_tokens[(size_t)b * out_stride + slot];
+    if ((unsigned int)tok >= (unsigned int)V) return;
+    unsigned int bits = (unsigned int)reinterpret_cast<const unsigned short*>(logits + (size_t)b * ld)[tok] << 16;
+    if (bits == 0x80000000u) bits = 0u;  // -0 -> +0, as in the top list's keys
+    out_logprobs[(size_t)b * cap + slot] = (__uint_as_float(bits) - lse_m[b]) - lse_logS[b];
+}
+
 static int launch_keys(const void* logits, int ld, int B, int V, int tok_offset, const float* temps,
                        const long long* seeds, const int* positions, void* result, hipStream_t s) {
     const int nseg = 32;
@@ -633,5 +887,39 @@ MRSUM_API int mrsum_sample_keys_filtered(const void* logits, int ld, int B, int 
     seg_len = (seg_len + 7) & ~7;
     sample_kernel<true><<<dim3(nseg, B), 256, 0, s>>>((const bf16*)logits, ld, V, 0, temps, seeds, positions,
                                                       (unsigned long long*)result, seg_len, thresh);
+    return (int)hipGetLastError();
+}
+
+// Log-probabilities of whole rows (tok_offset 0), after mrsum_constrain / mrsum_penalize and BEFORE any sampler
+// launch on stream s (capturable; the logits are only read).  lp_n: -1 = off, else the row's top-list length
+// 0..20.  A live row (lp_n >= 0, not done, gen_count < cap) gets its top list written into record gen_count[b]
+// of out_top_tok / out_top_lp (B x cap x 20) and lse_m / lse_logS / lp_slot[b] = gen_count[b] for
+// mrsum_logprobs_pick; every other row gets lp_slot[b] = -1 and nothing else.  seg_ms (B x 32 float2) and
+// seg_keys (B x 32 x 20 u64) are scratch, rewritten for every live row: no state is carried between launches.
+MRSUM_API int mrsum_logprobs(const void* logits, int ld, int B, int V, const int* lp_n, const int* gen_count,
+                             const int* done, int cap, void* seg_ms, void* seg_keys, float* lse_m, float* lse_logS,
+                             int* lp_slot, int* out_top_tok, float* out_top_lp, hipStream_t s) {
+    if (B <= 0) return 0;
+    int seg_len = ceil_div(V, LP_SEGS);
+    seg_len = (seg_len + 7) & ~7;
+    logprobs_seg_kernel<<<dim3(LP_SEGS, B), LP_THREADS, 0, s>>>((const bf16*)logits, ld, V, lp_n, gen_count, done, cap,
+                                                                seg_len, (float2*)seg_ms,
+                                                                (unsigned long long*)seg_keys);
+    int e = (int)hipGetLastError();
+    if (e) return e;
+    logprobs_merge_kernel<<<B, 64, 0, s>>>(lp_n, gen_count, done, cap, (const float2*)seg_ms,
+                                           (const unsigned long long*)seg_keys, lse_m, lse_logS, lp_slot, out_top_tok,
+                                           out_top_lp);
+    return (int)hipGetLastError();
+}
+
+// After the finish kernel (plain, row-stops, or the TP one): out_logprobs[b, lp_slot[b]] = the log-probability
+// of the token the finish appended at out_tokens[b, lp_slot[b]], for every row with lp_slot[b] >= 0.
+MRSUM_API int mrsum_logprobs_pick(const void* logits, int ld, int B, int V, const int* out_tokens, int out_stride,
+                                  const int* lp_slot, const float* lse_m, const float* lse_logS, float* out_logprobs,
+                                  int cap, hipStream_t s) {
+    if (B <= 0) return 0;
+    logprobs_pick_kernel<<<ceil_div(B, 64), 64, 0, s>>>((const bf16*)logits, ld, V, out_tokens, out_stride, lp_slot,
+                                                        lse_m, lse_logS, out_logprobs, cap, B);
     return (int)hipGetLastError();
 }

@@ -44,6 +44,7 @@ MAX_WINDOW = 256  # decode steps between host syncs when no row can stop early (
 _I32_MAX = 2 ** 31 - 1  # DecodeState.top_k is int32; any k >= the vocabulary size means "off"
 MAX_LOGIT_BIAS = 300  # logit_bias entries per request (OpenAI's limit; DecodeState.bias_tok row width)
 MAX_STOP_IDS = 4  # stop_token_ids per request (DecodeState.stop_ids row width, sampler.hip STOP_SLOTS)
+MAX_TOP_LOGPROBS = ops.LOGPROBS_TOP  # top_logprobs per request (OpenAI's limit; the record store's list width)
 
 
 def _always() -> bool:
@@ -63,6 +64,11 @@ def _any_penalised(seqs) -> bool:
 def _any_constrained(seqs) -> bool:
     """Whether any of these sequences carries a logit bias, a minimum length or stop ids of its own."""
     return any(s.params.constrained for s in seqs)
+
+
+def _any_logprobs(seqs) -> bool:
+    """Whether any of these sequences asks for the log-probabilities of its tokens."""
+    return any(s.params.logprobs for s in seqs)
 
 
 @dataclass
@@ -86,6 +92,11 @@ class SamplingParams:
     logit_bias: Union[Mapping[int, float], Sequence[Tuple[int, float]], None] = None
     min_tokens: int = 0
     stop_token_ids: Sequence[int] = ()
+    # log-probabilities (ops.reference.token_logprobs) of every generated token, taken from the logits the
+    # sampler sees (after the constraints and penalties, at temperature 1, before top-k / top-p), and with
+    # top_logprobs = n in [0, 20] the n most likely tokens of every step; they never change what is sampled
+    logprobs: bool = False
+    top_logprobs: int = 0
 
     @property
     def constrained(self) -> bool:
@@ -155,6 +166,13 @@ class SamplingParams:
             raise ValueError("top_k must be an integer >= 0, got %r" % (k,))
         if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 < p <= 1.0:
             raise ValueError("top_p must be a number in (0, 1], got %r" % (p,))
+        if not isinstance(self.logprobs, bool):
+            raise ValueError("logprobs must be a boolean, got %r" % (self.logprobs,))
+        n = self.top_logprobs
+        if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= MAX_TOP_LOGPROBS:
+            raise ValueError("top_logprobs must be an integer in [0, %d], got %r" % (MAX_TOP_LOGPROBS, n))
+        if n > 0 and not self.logprobs:
+            raise ValueError("top_logprobs needs logprobs")
 
 
 @dataclass
@@ -162,6 +180,10 @@ class GenOutput:
     token_ids: List[int]
     prompt_len: int
     finish_reason: str  # "stop" | "length"
+    # with SamplingParams.logprobs: the log-probability of every token of token_ids, and per token its
+    # top_logprobs most likely (token, log-probability) pairs, most likely first; None unless asked for
+    logprobs: Optional[List[float]] = None
+    top_logprobs: Optional[List[List[Tuple[int, float]]]] = None
 
 
 @dataclass
@@ -183,6 +205,9 @@ class ImportedPrefill:
     whole pages; rows past the prompt are ignored).  See LLMEngine.prefill_export."""
     first_token: int
     kv: Optional[torch.Tensor]
+    # the first token's log-probability record, (lp, [(token, lp)]), for a request that asks for logprobs
+    # (the engine that sampled the token took it; without it such a request is refused)
+    first_logprobs: Optional[Tuple[float, List[Tuple[int, float]]]] = None
 
 
 class DecodeState:
@@ -220,6 +245,10 @@ class DecodeState:
         self.bias_n = torch.zeros(max_seqs, **i32)
         self.min_new = torch.zeros(max_seqs, **i32)
         self.stop_ids = torch.full((max_seqs, MAX_STOP_IDS), -1, **i32)
+        # log-probability records (ops.reference.token_logprobs): -1 = off, else the row's top-list length
+        # 0..20; the records themselves live in the store, allocated when a request first asks
+        self.lp_n = torch.full((max_seqs,), -1, **i32)
+        self.lp = ops.LogprobStore(max_seqs, max_new_cap, device)
         self.filter_ws = None
         if self.temps.is_cuda:
             from ..ops.hip import FilterWorkspace
@@ -240,7 +269,7 @@ class DecodeState:
 
     _ROW_FIELDS = ("next_ids", "positions", "block_tables", "gen_count", "max_new", "out_tokens", "done", "result",
                    "temps", "seeds", "top_k", "top_p", "thresh", "rep_pen", "freq_pen", "pres_pen",
-                   "bias_tok", "bias_val", "bias_n", "min_new", "stop_ids")
+                   "bias_tok", "bias_val", "bias_n", "min_new", "stop_ids", "lp_n")
 
     def view(self, start: int, n: int) -> "DecodeState":
         v = object.__new__(DecodeState)
@@ -250,15 +279,20 @@ class DecodeState:
         v.seq_idx = self.seq_idx[:n]
         v.eos, v.eos_ids = self.eos, self.eos_ids
         v.filter_ws = self.filter_ws
+        v.lp = self.lp.view(start, n)
+        v.logprobs = False  # set by the engine on the view of a batch with a row that asks for logprobs
         v.filtered = False  # set by the engine on the view of a batch with a top-k / top-p row
         v.penalised = False  # ... and of a batch with a penalised row
         v.constrained = False  # ... and of a batch with a constrained row (bias / min_new / stop_ids)
         return v
 
-    def move_row(self, src: int, dst: int) -> None:
+    def move_row(self, src: int, dst: int, records: bool = True) -> None:
+        """``records``: also the row's log-probability records (a row that never asked has none)."""
         for f in self._ROW_FIELDS:
             t = getattr(self, f)
             t[dst].copy_(t[src])
+        if records:
+            self.lp.move_row(src, dst)
 
     def park_row(self, i: int) -> None:
         """Idle slot: stopped, position 0, all pages -> scratch page 0."""
@@ -269,6 +303,7 @@ class DecodeState:
         self.rep_pen[i], self.freq_pen[i], self.pres_pen[i] = 1.0, 0.0, 0.0
         self.bias_n[i], self.min_new[i] = 0, 0
         self.stop_ids[i].fill_(-1)
+        self.lp_n[i] = -1
 
 
 class _CPExchange:
@@ -414,7 +449,8 @@ class LLMEngine:
         self._workspaces: Dict[Tuple[int, int], object] = {}
         self.stats = {"prefill_tokens": 0, "prefill_s": 0.0, "decode_steps": 0, "decode_tokens": 0,
                       "decode_s": 0.0, "generate_calls": 0, "graph_captures": 0, "peak_active": 0,
-                      "filtered_steps": 0, "penalised_steps": 0, "constrained_steps": 0}
+                      "filtered_steps": 0, "penalised_steps": 0, "constrained_steps": 0,
+                      "logprob_steps": 0}
         self._ignore_eos = False  # set for the length of a generate(ignore_eos=True)
 
     # ------------------------------------------------------------------ helpers
@@ -538,12 +574,16 @@ class LLMEngine:
         v.constrained = _any_constrained(seqs)  # gen_count is 0: the first token is constrained like any other
         if v.constrained:
             self.stats["constrained_steps"] += 1
+        v.logprobs = _any_logprobs(seqs)  # token 0 has a record like every other
+        if v.logprobs:
+            self.stats["logprob_steps"] += 1
         self._sample(logits, v)
 
     def _gather(self, seqs: Sequence[_Seq]) -> bool:
         """Whether the forward that feeds these sequences' sampler gathers the logits over the TP group: always
-        without vocab-parallel sampling, and for a filtered batch (the filter takes whole rows)."""
-        return not self.model.tp_sampling or _any_filtered(seqs)
+        without vocab-parallel sampling, and for a filtered batch or one with a row that asks for logprobs
+        (the filter and the logprobs kernels take whole rows)."""
+        return not self.model.tp_sampling or _any_filtered(seqs) or _any_logprobs(seqs)
 
     def _prefill_pass(self, seqs: List[_Seq], spans, paged: bool, final: bool = True) -> None:
         """One packed forward over prompt slices ``spans`` [(start, end)] of ``seqs``; on the final pass,
@@ -565,62 +605,77 @@ class LLMEngine:
         shard (every rank holds the same out_tokens).
         ``st_view.constrained``: some row has a logit bias, a minimum length or stop ids of its own; the
         logits are constrained before anything else, on the same columns as the penalties, and the sampler
-        ends in the finish that honours the rows' stop ids."""
-        shard = self.model.tp_sampling and not st_view.filtered
+        ends in the finish that honours the rows' stop ids.
+        ``st_view.logprobs``: some row asks for log-probabilities; they are taken from the whole rows (gathered
+        on a vocab-parallel engine, as for a filter) once constrained and penalised, before the sampler, and
+        the sampled token's is picked after it."""
+        whole = st_view.filtered or st_view.logprobs
+        shard = self.model.tp_sampling and not whole
         if st_view.constrained:
             ops.constrain(logits, st_view, self.model.vocab_offset if shard else 0)
         if st_view.penalised:
             ops.penalize(logits, st_view, self.model.vocab_offset if shard else 0)
+        if st_view.logprobs:
+            ops.logprobs(logits, st_view)
         if st_view.filtered:
             ops.sample(logits, st_view, filtered=True)
-        elif self.model.tp_sampling:  # local vocab shard + cross-rank max of the 8-byte Gumbel keys
+        elif shard:  # local vocab shard + cross-rank max of the 8-byte Gumbel keys
             ops.sample_tp(logits, st_view, self.model.vocab_offset, self.model.custom_ar.max_u64_)
         else:
             ops.sample(logits, st_view)
+        if st_view.logprobs:
+            ops.logprobs_pick(logits, st_view)
 
     def _decode_once(self, B: int, filtered: bool = False, penalised: bool = False,
-                     constrained: bool = False) -> None:
+                     constrained: bool = False, logprobs: bool = False) -> None:
         st = self.state
         logits = self.model.decode(st.next_ids[:B], st.positions[:B], st.seq_idx[:B], st.block_tables[:B],
                                    self.kv.k, self.kv.v, workspace=self._workspace(B),
-                                   gather=filtered or not self.model.tp_sampling)
+                                   gather=filtered or logprobs or not self.model.tp_sampling)
         v = st.view(0, B)
         v.filtered = filtered
         v.penalised = penalised
         v.constrained = constrained
+        v.logprobs = logprobs
         self._sample(logits, v)
 
     def _decode_steps(self, B: int, steps: int, filtered: bool = False, penalised: bool = False,
-                      constrained: bool = False) -> None:
+                      constrained: bool = False, logprobs: bool = False) -> None:
         if filtered:
             self.stats["filtered_steps"] += steps
         if penalised:
             self.stats["penalised_steps"] += steps
         if constrained:
             self.stats["constrained_steps"] += steps
+        if logprobs:
+            self.stats["logprob_steps"] += steps
         if self._fault_delay is not None and int(self._fault_delay[0]) == self.model.tp_rank \
                 and self.model.custom_ar is not None:
             delay, self._fault_delay = self._fault_delay[1], None  # once
             log.warning("fault injection: TP rank %d sleeps %.1f s before a decode window", self.model.tp_rank, delay)
             time.sleep(delay)
-        if not self.use_graphs or (filtered and self.model.tp_sampling):
-            # a filtered step of a vocab-parallel engine gathers the logits on RCCL, which stays outside
-            # any capture: it runs eagerly
+        if not self.use_graphs or ((filtered or logprobs) and self.model.tp_sampling):
+            # a filtered or logprob step of a vocab-parallel engine gathers the logits on RCCL, which stays
+            # outside any capture: it runs eagerly
             for _ in range(steps):
-                self._decode_once(B, filtered, penalised, constrained)
+                self._decode_once(B, filtered, penalised, constrained, logprobs)
             return
-        g = self._graphs.get(self._graph_key(B, filtered, penalised, constrained))
+        g = self._graphs.get(self._graph_key(B, filtered, penalised, constrained, logprobs))
         if g is None:
-            g = self._capture(B, filtered, penalised, constrained)
+            g = self._capture(B, filtered, penalised, constrained, logprobs)
         for _ in range(steps):
             g.replay()
 
-    def _graph_key(self, B: int, filtered: bool, penalised: bool = False, constrained: bool = False) -> tuple:
+    def _graph_key(self, B: int, filtered: bool, penalised: bool = False, constrained: bool = False,
+                   logprobs: bool = False) -> tuple:
         """Key of a decode graph: (bucket, context class), (bucket, context class, True) for the graph
         whose sampler filters, (bucket, context class, filtered, "pen") for the graphs that penalise
         first, and (bucket, context class, filtered, penalised, "con") for the graphs that constrain before
-        all that and finish with the rows' stop ids (all but the plain ones captured on first use;
-        ``capture_graphs`` captures the plain ones)."""
+        all that and finish with the rows' stop ids; the graphs that also take log-probabilities carry all
+        three flags and a trailing "lp" (all but the plain ones captured on first use; ``capture_graphs``
+        captures the plain ones)."""
+        if logprobs:
+            return (B, self._ctx_cls, filtered, penalised, constrained, "lp")
         if constrained:
             return (B, self._ctx_cls, filtered, penalised, "con")
         if penalised:
@@ -651,7 +706,8 @@ class LLMEngine:
         self._sync()
         return n
 
-    def _capture(self, B: int, filtered: bool = False, penalised: bool = False, constrained: bool = False):
+    def _capture(self, B: int, filtered: bool = False, penalised: bool = False, constrained: bool = False,
+                 logprobs: bool = False):
         # snapshot state rows the warm-up step will advance, run it eagerly once (lazy kernel-library
         # load, workspace and split-K ticket allocation), restore, then capture.
         st = self.state
@@ -659,18 +715,19 @@ class LLMEngine:
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
-            # (a filtered warm-up also allocates the filter workspace)
-            self._decode_once(B, filtered, penalised, constrained)
+            # (a filtered warm-up also allocates the filter workspace, a logprob one the record store; the
+            # record it writes is the one the first replayed step writes again)
+            self._decode_once(B, filtered, penalised, constrained, logprobs)
         torch.cuda.current_stream(self.device).wait_stream(s)
         for f, t in snap.items():
             getattr(st, f)[:B].copy_(t)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._decode_once(B, filtered, penalised, constrained)
+            self._decode_once(B, filtered, penalised, constrained, logprobs)
         # capture does not execute; restore anyway in case the backend ran the work
         for f, t in snap.items():
             getattr(st, f)[:B].copy_(t)
-        self._graphs[self._graph_key(B, filtered, penalised, constrained)] = g
+        self._graphs[self._graph_key(B, filtered, penalised, constrained, logprobs)] = g
         self.stats["graph_captures"] += 1
         return g
 
@@ -772,6 +829,8 @@ class LLMEngine:
         if max(p) >= self.cfg.vocab_size or min(p) < 0:
             raise ValueError("token id out of range")
         sp.validate(self.cfg.vocab_size)
+        if imported is not None and sp.logprobs and imported.first_logprobs is None:
+            raise ValueError("a request that asks for logprobs needs its imported prefill's first_logprobs")
         return _Seq(i, p, replace(sp, max_new_tokens=mn), imported=imported)
 
     def _fit_ctx_class(self, seqs: Sequence[_Seq]) -> None:
@@ -795,6 +854,10 @@ class LLMEngine:
                 own = () if self._ignore_eos else s.params.stop_token_ids
                 if mn == 1 or tok in self.state.eos_ids or tok in own:
                     results[i] = GenOutput([tok], len(s.prompt), "length" if mn == 1 else "stop")  # done at prefill
+                    if s.params.logprobs:
+                        lp0, top0 = s.imported.first_logprobs
+                        results[i].logprobs = [float(lp0)]
+                        results[i].top_logprobs = [list(top0)[:s.params.top_logprobs]]
                     finished.append(i)
                     continue
             waiting.append(s)
@@ -839,7 +902,7 @@ class LLMEngine:
                 if t_window_end is not None:  # host work + prefill between two windows of running rows
                     self.stats["max_window_gap_s"] = max(self.stats.get("max_window_gap_s", 0.0), t0 - t_window_end)
                 self._decode_steps(B, steps, _any_filtered(active), _any_penalised(active),
-                                   _any_constrained(active))
+                                   _any_constrained(active), _any_logprobs(active))
                 self._sync()
                 t_window_end = time.perf_counter()
                 self.stats["decode_s"] += t_window_end - t0
@@ -858,6 +921,9 @@ class LLMEngine:
                     ids = toks[i, :g].tolist()
                     reason = "length" if g >= s.params.max_new_tokens else "stop"
                     results[s.rid] = GenOutput(ids, len(s.prompt), reason)
+                    if s.params.logprobs:
+                        results[s.rid].logprobs, results[s.rid].top_logprobs = st.lp.read(
+                            i, g, s.params.top_logprobs)
                     finished.append(s.rid)
                     self.stats["decode_tokens"] += g
                     self.kv.alloc.free(s.pages)
@@ -936,6 +1002,7 @@ class LLMEngine:
             st.top_p[s.slot] = float(s.params.top_p)
             self._set_penalties(s.slot, s.params)
             self._set_constraints(s.slot, s.params)
+            self._set_logprobs(s.slot, s.params)
             st.result[s.slot] = 0
             if s.imported is not None:  # no forward pass: KV + first token come from elsewhere
                 self._install(s)
@@ -1007,6 +1074,9 @@ class LLMEngine:
         stops = [] if self._ignore_eos else [int(t) for t in params.stop_token_ids]
         st.stop_ids[slot].copy_(torch.tensor(stops + [-1] * (MAX_STOP_IDS - len(stops)), dtype=torch.int32))
 
+    def _set_logprobs(self, slot: int, params: SamplingParams) -> None:
+        self.state.lp_n[slot] = int(params.top_logprobs) if params.logprobs else -1
+
     def _setup_slot(self, s: _Seq, row: torch.Tensor) -> None:
         """Decode-state row of ``s`` at ``s.slot``: its pages, budget and sampling parameters."""
         st = self.state
@@ -1020,6 +1090,7 @@ class LLMEngine:
         st.top_p[s.slot] = float(s.params.top_p)
         self._set_penalties(s.slot, s.params)
         self._set_constraints(s.slot, s.params)
+        self._set_logprobs(s.slot, s.params)
         st.result[s.slot] = 0
 
     def _interleaved_pass(self, prefilling: List[_Seq], active: List[_Seq], max_parts: Optional[int] = None) -> None:
@@ -1091,6 +1162,14 @@ class LLMEngine:
             self.kv.v.index_copy_(1, idx, kv[1])
         i = s.slot
         st.out_tokens[i, 0] = int(imp.first_token)
+        if s.params.logprobs:  # record 0 was taken where the token was sampled
+            lp0, top0 = imp.first_logprobs
+            top0 = list(top0)[:s.params.top_logprobs]
+            st.lp.out_logprobs[i, 0] = float(lp0)
+            if top0:
+                st.lp.out_top_tok[i, 0, :len(top0)].copy_(torch.tensor([int(t) for t, _ in top0], dtype=torch.int32))
+                st.lp.out_top_lp[i, 0, :len(top0)].copy_(torch.tensor([float(x) for _, x in top0],
+                                                                      dtype=torch.float32))
         st.next_ids[i] = int(imp.first_token)
         st.gen_count[i] = 1
         st.positions[i] = n
@@ -1144,7 +1223,8 @@ class LLMEngine:
                 chunks[s.rid] = [torch.stack([k[:, :, g * hl:(g + 1) * hl], v[:, :, g * hl:(g + 1) * hl]])
                                  .reshape(-1) for g in range(groups)]
 
-        one = [replace(p, max_new_tokens=1, min_tokens=min(p.min_tokens, 1)) for p in params]
+        one = [replace(p, max_new_tokens=1, min_tokens=min(p.min_tokens, 1), logprobs=False, top_logprobs=0)
+               for p in params]  # (tokens only: a stage that asks for logprobs does not use the hand-off)
         outs = self.generate(prompts, one, ignore_eos=ignore_eos, on_prefill=grab)
         firsts = [o.token_ids[0] for o in outs]
         packs = [torch.cat([chunks[i][g] for i in range(len(prompts))]) if prompts else
@@ -1191,7 +1271,8 @@ class LLMEngine:
         import torch.distributed as dist
         if self.model.tp_size != 1 or self.model.hkv % world or self.kv.fp8:
             raise ValueError("prefill_export_cp needs a TP=1 bf16-KV engine and Hkv divisible by %d" % world)
-        s = self._new_seq(0, prompt, replace(params, max_new_tokens=1, min_tokens=min(params.min_tokens, 1)))
+        s = self._new_seq(0, prompt, replace(params, max_new_tokens=1, min_tokens=min(params.min_tokens, 1),
+                                             logprobs=False, top_logprobs=0))
         n = len(s.prompt)
         if n < 2 * world:
             raise ValueError("prompt of %d tokens is too short for context parallelism over %d ranks" % (n, world))
@@ -1210,6 +1291,7 @@ class LLMEngine:
             st.top_k[0], st.top_p[0] = min(int(params.top_k), _I32_MAX), float(params.top_p)
             self._set_penalties(0, params)
             self._set_constraints(0, s.params)
+            self._set_logprobs(0, s.params)
             slices = self.cp_slices(n, world)
             mine = [(b, e) for b, e in slices[rank] if e > b]
             if len(mine) != len(slices[rank]):  # n >= 2 world: every zigzag chunk holds a token
@@ -1259,7 +1341,7 @@ class LLMEngine:
         n_old = len(active)
         for new_slot, s in enumerate(keep):
             if s.slot != new_slot:
-                st.move_row(s.slot, new_slot)
+                st.move_row(s.slot, new_slot, records=s.params.logprobs)
                 s.slot = new_slot
         for i in range(len(keep), n_old):
             st.park_row(i)

@@ -73,14 +73,32 @@ def sampling_params(req: GenRequest, base_seed: int, config=None):
     """The engine's SamplingParams of one request: its budget and temperature, the seed derived from
     its text, its top-k / top-p filters (the request's own, else $TOP_K / $TOP_P of ``config``) and its
     frequency / presence / repetition penalties (likewise), its logit bias and minimum length (likewise) and
-    its stop token ids."""
+    its stop token ids, and whether it asks for log-probabilities."""
     from .engine import SamplingParams
     top_k, top_p = request_filters(req, config)
     freq, pres, rep = request_penalties(req, config)
     bias, min_tokens, stops = request_constraints(req, config)
     return SamplingParams(req.max_tokens, req.temperature, _req_seed(base_seed, req), top_k=top_k, top_p=top_p,
                           frequency_penalty=freq, presence_penalty=pres, repetition_penalty=rep,
-                          logit_bias=bias or None, min_tokens=min_tokens, stop_token_ids=tuple(stops))
+                          logit_bias=bias or None, min_tokens=min_tokens, stop_token_ids=tuple(stops),
+                          logprobs=bool(req.logprobs), top_logprobs=int(req.top_logprobs or 0))
+
+
+def logprobs_record(o) -> Dict[str, Any]:
+    """{"lp": GenResult.extra["logprobs"]} of an engine GenOutput that carries log-probabilities, else {}: plain
+    lists ({"token_ids", "token_logprobs", "top": [[[id, lp], ...] per token]}), so the record survives the
+    JSON of the DP all-gather and of the serve broadcast (-inf travels as -Infinity)."""
+    if o.logprobs is None:
+        return {}
+    return {"lp": {"token_ids": [int(t) for t in o.token_ids], "token_logprobs": [float(x) for x in o.logprobs],
+                   "top": [[[int(t), float(x)] for t, x in step] for step in (o.top_logprobs or [])]}}
+
+
+def _extra(finish_reason: str, lp: Optional[Dict[str, Any]]) -> Dict[str, Any]:
+    extra: Dict[str, Any] = {"finish_reason": finish_reason}
+    if lp is not None:
+        extra["logprobs"] = lp
+    return extra
 
 
 def parse_parallel(spec: str, world: int) -> Dict[str, int]:
@@ -444,6 +462,10 @@ class LocalEngineProvider(Provider):
         (parallel/plan.py)."""
         if not self.handoff or not reqs:
             return False
+        if any(r.logprobs for r in reqs):
+            # the hand-off samples the first token on another engine, which keeps no log-probability record:
+            # the TP engine prefills such a stage itself
+            return False
         if len(reqs) > 1:
             return True
         k = k or self.par.world
@@ -588,7 +610,7 @@ class LocalEngineProvider(Provider):
                 outs = self.tp_engine_for(k).generate(sub_p, sub_sp, ignore_eos=self.ignore_eos, imported=imported)
                 for i, o in zip(mine, outs):
                     local.append({"i": i, "text": self.tokenizer.decode(o.token_ids), "pt": o.prompt_len,
-                                  "ct": len(o.token_ids), "fr": o.finish_reason})
+                                  "ct": len(o.token_ids), "fr": o.finish_reason, **logprobs_record(o)})
             except Exception as e:  # noqa: BLE001 -- SPMD inside the group: its every rank raises alike
                 msg = "rank %d: %s: %s" % (rank, type(e).__name__, e)
                 log.error("TP=%d group %d failed on %d requests: %s", k, rank // k, len(mine), msg)
@@ -628,7 +650,7 @@ class LocalEngineProvider(Provider):
             log.error("TP stage failed: %s", "; ".join(errs))
             return [GenResult("", error="; ".join(errs)) for _ in reqs]
         return [GenResult(self.tokenizer.decode(o.token_ids), o.prompt_len, len(o.token_ids), 0.0,
-                          extra={"finish_reason": o.finish_reason}) for o in outs]
+                          extra=_extra(o.finish_reason, logprobs_record(o).get("lp"))) for o in outs]
 
     async def generate_batch(self, reqs: Sequence[GenRequest]) -> List[GenResult]:
         t0 = time.perf_counter()
@@ -672,7 +694,7 @@ class LocalEngineProvider(Provider):
                     ignore_eos=self.ignore_eos)
                 for i, o in zip(mine, outs):
                     local.append({"i": i, "text": self.tokenizer.decode(o.token_ids), "pt": o.prompt_len,
-                                  "ct": len(o.token_ids), "fr": o.finish_reason})
+                                  "ct": len(o.token_ids), "fr": o.finish_reason, **logprobs_record(o)})
             except Exception as e:  # noqa: BLE001 -- never skip the all-gather below: the peers are in it
                 msg = "rank %d: %s: %s" % (self.par.rank, type(e).__name__, e)
                 log.error("engine failed on %d requests: %s", len(mine), msg)
@@ -732,7 +754,7 @@ class LocalEngineProvider(Provider):
 
         def rec(key, idx, o):
             return {key: idx, "text": self.tokenizer.decode(o.token_ids), "pt": o.prompt_len, "ct": len(o.token_ids),
-                    "fr": o.finish_reason}
+                    "fr": o.finish_reason, **logprobs_record(o)}
 
         def feeder(done):
             new = []
@@ -806,10 +828,10 @@ class LocalEngineProvider(Provider):
 
 
 def _result(r: Dict[str, Any]) -> GenResult:
-    """GenResult of an all-gathered result record ({"text", "pt", "ct", "fr"} or {"err"})."""
+    """GenResult of an all-gathered result record ({"text", "pt", "ct", "fr"[, "lp"]} or {"err"})."""
     if "err" in r:
         return GenResult("", error=r["err"])
-    return GenResult(r["text"], r["pt"], r["ct"], 0.0, extra={"finish_reason": r["fr"]})
+    return GenResult(r["text"], r["pt"], r["ct"], 0.0, extra=_extra(r["fr"], r.get("lp")))
 
 
 def _rccl_bandwidth(group, hidden: int, device, rows: int = 4096) -> float:

@@ -261,6 +261,125 @@ def constrain(logits, st, tok_offset=0):
                                        st.min_new[:n], st.stop_ids[:n], st.eos, st.done[:n], tok_offset)
 
 
+LOGPROBS_TOP = 20  # longest top list (OpenAI's top_logprobs limit; sampler.hip LP_TOP)
+LOGPROBS_SEGS = 32  # sampler.hip LP_SEGS: segments of a row the logprobs kernel scans
+
+
+class LogprobStore:
+    """Log-probability records of the decode slots, and the logprobs kernels' per-step scratch: ``rows`` x
+    ``cap`` steps of ``out_logprobs`` (fp32, the sampled token's) and ``out_top_tok`` / ``out_top_lp``
+    ([rows, cap, 20] int32 / fp32, the top lists; entries past a row's list are never written, entries past
+    the vocabulary are -1 / -inf), 164 bytes per step, plus ``lse_m`` / ``lse_logS`` / ``lp_slot`` ([rows])
+    and the segment scratch ``seg_ms`` / ``seg_keys``.  Allocated on first use -- never inside a graph
+    capture, where allocating is an error (the engine's warm-up step before a capture makes the first use).
+    ``view`` gives the same tensors restricted to a range of rows."""
+
+    _FIELDS = ("out_logprobs", "out_top_tok", "out_top_lp", "lse_m", "lse_logS", "lp_slot", "seg_ms", "seg_keys")
+
+    def __init__(self, rows: int, cap: int, device, _base=None, _start: int = 0):
+        self.rows, self.cap, self.device = int(rows), int(cap), torch.device(device)
+        self._base, self._start = (self if _base is None else _base), _start
+        self._t = None
+        self._ok = False  # set by ops.hip once it has checked this view's layout
+
+    def view(self, start: int, n: int) -> "LogprobStore":
+        return LogprobStore(n, self.cap, self.device, self._base, self._start + start)
+
+    @property
+    def allocated(self) -> bool:
+        return self._base._t is not None
+
+    def ensure(self) -> "LogprobStore":
+        base = self._base
+        if base._t is None:
+            if base.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise ValueError("logprobs: the record store must exist before a graph capture")
+            R, C, dev = base.rows, base.cap, base.device
+            f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+            base._t = {
+                "out_logprobs": torch.zeros(R, C, **f32),
+                "out_top_tok": torch.full((R, C, LOGPROBS_TOP), -1, **i32),
+                "out_top_lp": torch.zeros(R, C, LOGPROBS_TOP, **f32),
+                "lse_m": torch.zeros(R, **f32), "lse_logS": torch.zeros(R, **f32),
+                "lp_slot": torch.full((R,), -1, **i32),
+                "seg_ms": torch.zeros(R, LOGPROBS_SEGS, 2, **f32),
+                "seg_keys": torch.zeros(R, LOGPROBS_SEGS, LOGPROBS_TOP, dtype=torch.int64, device=dev),
+            }
+        return self
+
+    def __getattr__(self, name):
+        if name in LogprobStore._FIELDS:
+            t = self.ensure()._base._t[name][self._start:self._start + self.rows]
+            self.__dict__[name] = t  # (the slice is fixed once the store exists: later reads skip this hook)
+            return t
+        raise AttributeError(name)
+
+    def move_row(self, src: int, dst: int) -> None:
+        """Row ``src``'s records -> row ``dst`` (slot compaction)."""
+        if self.allocated:
+            for f in ("out_logprobs", "out_top_tok", "out_top_lp"):
+                t = getattr(self, f)
+                t[dst].copy_(t[src])
+
+    def read(self, row: int, steps: int, top_n: int):
+        """The first ``steps`` records of ``row`` on the host: ([lp], [[(token, lp)] per step]), the top
+        lists cut to ``top_n`` entries (fewer when the vocabulary is smaller)."""
+        lps = self.out_logprobs[row, :steps].cpu().tolist()
+        k = max(0, min(int(top_n), LOGPROBS_TOP))
+        tok = self.out_top_tok[row, :steps, :k].cpu().tolist()
+        tlp = self.out_top_lp[row, :steps, :k].cpu().tolist()
+        return lps, [[(int(t), float(x)) for t, x in zip(tr, lr) if t >= 0] for tr, lr in zip(tok, tlp)]
+
+
+def logprobs(logits, st):
+    """Log-probability records of this step (reference.token_logprobs), taken from the rows ``logits`` as the
+    sampler is about to see them: call after ``constrain`` / ``penalize`` and before ``sample``.  Row b with
+    ``st.lp_n[b]`` >= 0 (its top-list length, 0..20) that is not done and whose step ``g = st.gen_count[b]``
+    is below the store's width gets its top list written into record g of ``st.lp`` (a LogprobStore) and
+    ``lse_m`` / ``lse_logS`` / ``lp_slot[b] = g`` for ``logprobs_pick``; every other row gets ``lp_slot[b]``
+    = -1 and nothing else.  Whole rows only; the logits are not modified."""
+    if _use_hip(logits):
+        from . import hip
+        return hip.logprobs(logits, st)
+    B, V = logits.shape
+    lp = st.lp.ensure()
+    lp.lp_slot[:B] = -1
+    live = [b for b in range(B)
+            if int(st.lp_n[b]) >= 0 and not int(st.done[b]) and int(st.gen_count[b]) < lp.cap]
+    if not live:
+        return
+    ns = [min(int(st.lp_n[b]), LOGPROBS_TOP) for b in live]
+    x = logits[live].to(torch.float64)
+    _, tops = reference.token_logprobs(x, ns)
+    m = x.max(dim=1).values
+    logS = torch.log(torch.exp(x - m[:, None]).sum(dim=1))
+    for i, b in enumerate(live):
+        g = int(st.gen_count[b])
+        top = tops[i] + [(-1, float("-inf"))] * (ns[i] - len(tops[i]))
+        if top:
+            lp.out_top_tok[b, g, :ns[i]] = torch.tensor([t for t, _ in top], dtype=torch.int32)
+            lp.out_top_lp[b, g, :ns[i]] = torch.tensor([v for _, v in top], dtype=torch.float32)
+        lp.lse_m[b], lp.lse_logS[b], lp.lp_slot[b] = float(m[i]), float(logS[i]), g
+
+
+def logprobs_pick(logits, st):
+    """After ``sample``: the log-probability of the token just appended by every row ``logprobs`` gave a
+    slot (``st.lp.lp_slot[b]`` >= 0), read from the still unmodified ``logits``, into
+    ``st.lp.out_logprobs[b, slot]`` -- the same number as the token's entry in the top list, when it is there."""
+    if _use_hip(logits):
+        from . import hip
+        return hip.logprobs_pick(logits, st)
+    B, V = logits.shape
+    lp = st.lp.ensure()
+    rows = [b for b in range(B) if int(lp.lp_slot[b]) >= 0]
+    if not rows:
+        return
+    ref, _ = reference.token_logprobs(logits[rows], 0)
+    for i, b in enumerate(rows):
+        slot = int(lp.lp_slot[b])
+        lp.out_logprobs[b, slot] = float(ref[i, int(st.out_tokens[b, slot])])
+
+
 def sample_tp(logits, st, tok_offset, max_reduce):
     """Vocab-parallel sampling over this rank's logits shard (GPU only; see hip.sample_tp)."""
     from . import hip

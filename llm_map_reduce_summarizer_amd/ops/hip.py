@@ -66,6 +66,8 @@ _SIGS = {
     "mrsum_constrain": [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mrsum_sample_finish_stops": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _c_int, _vp],
     "mrsum_sample_keys_filtered": [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mrsum_logprobs": [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mrsum_logprobs_pick": [_vp, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp],
     "mrsum_sample_thresh": [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mrsum_sample_filtered": [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                               _vp, _vp, _c_int, _vp, _vp, _vp],
@@ -759,6 +761,68 @@ def constrain(logits: torch.Tensor, st, tok_offset: int = 0) -> torch.Tensor:
                                   _p(st.bias_val), st.bias_tok.stride(0), _p(st.bias_n), _p(st.gen_count),
                                   _p(st.min_new), _p(st.stop_ids), _p(st.eos), _p(st.done), _stream()), "constrain")
     return logits
+
+
+LOGPROBS_TOP = 20  # sampler.hip LP_TOP: entries of a top list
+LOGPROBS_SEGS = 32  # sampler.hip LP_SEGS
+
+
+def _logprob_store_ok(st, B: int, device, what: str):
+    """The state's LogprobStore (allocated here on first use, never in a capture), checked against the
+    layout the kernels index: contiguous rows of ``cap`` records, 20 entries per top list."""
+    _req(hasattr(st, "lp") and hasattr(st, "lp_n"), "%s: the state needs an lp_n row and an lp store" % what)
+    lp = st.lp
+    if lp._ok and lp.rows >= B and lp.device == device:  # (a view is checked once: its tensors never change)
+        return lp
+    lp.ensure()
+    cap = lp.cap
+    _req(lp.rows >= B and cap >= 1, "%s: the record store is smaller than the batch" % what)
+    for name, dtype, shape in (("out_logprobs", torch.float32, (cap,)),
+                               ("out_top_tok", torch.int32, (cap, LOGPROBS_TOP)),
+                               ("out_top_lp", torch.float32, (cap, LOGPROBS_TOP)),
+                               ("lse_m", torch.float32, ()), ("lse_logS", torch.float32, ()),
+                               ("lp_slot", torch.int32, ()), ("seg_ms", torch.float32, (LOGPROBS_SEGS, 2)),
+                               ("seg_keys", torch.int64, (LOGPROBS_SEGS, LOGPROBS_TOP))):
+        t = getattr(lp, name)
+        _req(t.device == device and t.dtype == dtype and t.is_contiguous() and tuple(t.shape[1:]) == shape
+             and t.shape[0] >= B, "%s: store field %s has the wrong layout" % (what, name))
+    _req(lp.seg_ms.data_ptr() % 8 == 0 and lp.seg_keys.data_ptr() % 8 == 0, "%s: misaligned scratch" % what)
+    lp._ok = True
+    return lp
+
+
+def logprobs(logits: torch.Tensor, st) -> None:
+    """Top lists and log-sum-exp of the rows ``logits`` [B, V] for this step (reference.token_logprobs), into
+    ``st.lp``: two launches (segments, merge), after constrain / penalize and before any sampler launch;
+    capturable; the logits are only read.  See ops.logprobs for which rows get a record."""
+    _bf16_cuda(logits)
+    _rows_ok(logits)
+    B, V = logits.shape
+    _req(V >= 1, "logprobs: empty rows")
+    lp = _logprob_store_ok(st, B, logits.device, "logprobs")
+    _req(st.lp_n.numel() >= B and st.gen_count.numel() >= B and st.done.numel() >= B,
+         "logprobs: state smaller than batch")
+    _i32(st.lp_n, st.gen_count, st.done)
+    _check(_fn("mrsum_logprobs")(_p(logits), logits.stride(0), B, V, _p(st.lp_n), _p(st.gen_count), _p(st.done),
+                                 lp.cap, _p(lp.seg_ms), _p(lp.seg_keys), _p(lp.lse_m), _p(lp.lse_logS),
+                                 _p(lp.lp_slot), _p(lp.out_top_tok), _p(lp.out_top_lp), _stream()), "logprobs")
+
+
+def logprobs_pick(logits: torch.Tensor, st) -> None:
+    """After the sampler's finish: ``st.lp.out_logprobs[b, slot]`` = the log-probability of
+    ``st.out_tokens[b, slot]`` for every row with ``slot = st.lp.lp_slot[b]`` >= 0, from the same ``logits``
+    ``logprobs`` read.  One launch, capturable."""
+    _bf16_cuda(logits)
+    _rows_ok(logits)
+    B, V = logits.shape
+    lp = _logprob_store_ok(st, B, logits.device, "logprobs_pick")
+    ot = st.out_tokens
+    _req(ot.is_cuda and ot.dtype == torch.int32 and ot.dim() == 2 and ot.stride(1) == 1 and ot.shape[0] >= B
+         and ot.shape[1] >= lp.cap,
+         "logprobs_pick: out_tokens must be int32 device rows of the batch, as wide as the record store")
+    _check(_fn("mrsum_logprobs_pick")(_p(logits), logits.stride(0), B, V, _p(ot), ot.stride(0), _p(lp.lp_slot),
+                                      _p(lp.lse_m), _p(lp.lse_logS), _p(lp.out_logprobs), lp.cap, _stream()),
+           "logprobs_pick")
 
 
 def sample_tp(logits: torch.Tensor, st, tok_offset: int, max_reduce) -> None:

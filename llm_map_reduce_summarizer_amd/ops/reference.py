@@ -575,6 +575,41 @@ def apply_constraints(logits: torch.Tensor, bias_tok, bias_val, bias_n, gen_coun
     return logits
 
 
+def token_logprobs(logits: torch.Tensor, top_n):
+    """Token log-probabilities of the rows ``logits`` [B, V] (or one row [V]) and their top lists: THE
+    definition of what ``logprobs`` / ``top_logprobs`` report, computed in float64 on the stored (bf16) values.
+
+    For a row x:  m = max(x),  S = sum_i exp(x_i - m),  lp(t) = (x_t - m) - log S.  A -inf logit (a ban, a
+    suppressed stop id) adds 0 to S and has lp -inf.  Rows that hold a NaN or +inf, or nothing but -inf,
+    are unspecified, as sampling from them is.
+
+    The rows are the ones the sampler sees: after apply_constraints and apply_penalties, before the
+    temperature and before the top-k / top-p filter (vLLM's processed logits, at T = 1).
+
+    ``top_n``: one int or one per row; a row's list holds its min(n, V) tokens of the largest value, values
+    compared as numbers (-0 equals +0), ties broken by the lower token id, each with its lp.  n <= 0: empty.
+
+    Returns ``(lp, tops)``: lp float64 [B, V] on the CPU, tops a list of B lists of (token, lp)."""
+    x = logits.detach().to("cpu", torch.float64)
+    if x.dim() == 1:
+        x = x[None]
+    B, V = x.shape
+    ns = [int(top_n)] * B if isinstance(top_n, int) else [int(n) for n in top_n]
+    m = x.max(dim=1, keepdim=True).values
+    S = torch.exp(x - m).sum(dim=1, keepdim=True)
+    lp = (x - m) - torch.log(S)
+    tops = []
+    for b in range(B):
+        n = min(max(ns[b], 0), V)
+        if n == 0:
+            tops.append([])
+            continue
+        # a stable descending sort: equal values (and -0 / +0 compare equal) stay in token order
+        order = torch.sort(x[b], descending=True, stable=True).indices[:n]
+        tops.append([(int(t), float(lp[b, t])) for t in order])
+    return lp, tops
+
+
 def sample_tokens(logits: torch.Tensor, temps: torch.Tensor, seeds: torch.Tensor,
                   positions: torch.Tensor, thresh: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Gumbel-max sampling (argmax when temperature <= 0); ties -> lowest id.  ``thresh`` (fp32 [B],

@@ -58,6 +58,12 @@ class GenRequest:
     logit_bias: Any = None
     min_tokens: Optional[int] = None
     stop_token_ids: Optional[List[int]] = None
+    # log-probabilities of the generated tokens (engine SamplingParams.logprobs / top_logprobs: taken from the
+    # logits the sampler sees, at temperature 1); None = off / 0.  The local engine alone reports them, in
+    # GenResult.extra["logprobs"] = {"token_ids": [...], "token_logprobs": [...], "top": [[[id, lp], ...], ...]}
+    # (plain lists; a banned token's -inf survives the JSON of the result all-gather as -Infinity)
+    logprobs: Optional[bool] = None
+    top_logprobs: Optional[int] = None
 
 
 def logit_bias_pairs(lb: Any) -> List[Tuple[int, float]]:
@@ -269,7 +275,8 @@ class OpenAIProvider(_HTTPProvider):
         if pres != 0.0:
             body["presence_penalty"] = pres
         # logit_bias / min_tokens / stop_token_ids name token ids of the LOCAL tokenizer, which mean nothing
-        # to a hosted model: none of the three is sent
+        # to a hosted model: none of the three is sent; nor are logprobs / top_logprobs (their records carry
+        # local token ids, and the pipeline reads none from a hosted model)
         data = await self._post(headers, body)
         usage = data.get("usage", {})
         pt, ct = usage.get("prompt_tokens", 0), usage.get("completion_tokens", 0)
@@ -298,7 +305,8 @@ class AnthropicProvider(_HTTPProvider):
         if top_k > 0:
             body["top_k"] = top_k
         # (the Anthropic API has no frequency / presence / repetition penalty: none is sent; logit_bias /
-        # min_tokens / stop_token_ids name ids of the LOCAL tokenizer and are sent to no hosted API)
+        # min_tokens / stop_token_ids name ids of the LOCAL tokenizer and are sent to no hosted API; the API
+        # has no logprobs field either)
         data = await self._post(headers, body)
         text = data["content"][0]["text"]
         usage = data.get("usage") or {}

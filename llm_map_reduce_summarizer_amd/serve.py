@@ -21,7 +21,14 @@ far (sampler.hip's penalize kernel), on both endpoints; anything else is a 400. 
 from token id to a number in [-100, 100], at most 300 entries), ``min_tokens`` (an integer in [0, max tokens])
 and ``stop_token_ids`` (at most 4 token ids, the vLLM extension) constrain the sample on the GPU (sampler.hip's
 constrain kernel and its finish with row stop ids), on both endpoints; token ids are the served model's, and
-anything else is a 400.  Stop sequences and n > 1 are not supported (400).
+anything else is a 400.  ``logprobs`` (a boolean) and ``top_logprobs`` (an integer in [0, 20], which needs
+``logprobs: true``) on the chat endpoint return ``choices[0].logprobs.content``: per generated token its
+``token`` / ``bytes`` (the served tokenizer's, special tokens spelled out), its ``logprob`` and its
+``top_logprobs`` most likely tokens, computed on the GPU (sampler.hip's logprobs kernels) from the logits the
+sampler sees -- after logit_bias / min_tokens and the penalties, at temperature 1, before top-k / top-p; a
+banned token's -inf is sent as -9999.0.  Anything else is a 400, as are ``logprobs`` with ``stream: true`` and
+``logprobs`` / ``top_logprobs`` on ``/v1/messages`` (that API has no such field).  Stop sequences and n > 1 are
+not supported (400).
 
 Batching: HTTP handlers only enqueue; one engine thread owns the engine.  Single process
 (``ContinuousBatcher``): the first requests start a generate and every request that arrives while it runs
@@ -159,6 +166,30 @@ def _constraints(body: Dict[str, Any], max_tokens: int, vocab: Optional[int] = N
     return out
 
 
+MAX_TOP_LOGPROBS = 20  # OpenAI's limit, and the engine's (ops.LOGPROBS_TOP)
+NO_LOGPROB = -9999.0  # how a non-finite log-probability (a banned token's -inf) is sent: the OpenAI convention
+
+
+def _logprob_fields(body: Dict[str, Any]) -> Dict[str, Any]:
+    """``logprobs`` / ``top_logprobs`` of a chat-completions body as GenRequest fields (absent or null: off)."""
+    lp, n = body.get("logprobs"), body.get("top_logprobs")
+    if lp is not None and not isinstance(lp, bool):
+        raise BadRequest("logprobs must be a boolean")
+    if n is not None:
+        if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= MAX_TOP_LOGPROBS:
+            raise BadRequest("top_logprobs must be an integer in [0, %d]" % MAX_TOP_LOGPROBS)
+        if n > 0 and not lp:
+            raise BadRequest("top_logprobs needs logprobs: true")
+    if lp and body.get("stream"):
+        raise BadRequest("logprobs are not available on a streamed completion: send stream: false")
+    out: Dict[str, Any] = {}
+    if lp:
+        out["logprobs"] = True
+        if n:
+            out["top_logprobs"] = n
+    return out
+
+
 def openai_request(body: Dict[str, Any], default_temp: float = 1.0, vocab: Optional[int] = None) -> GenRequest:
     """GenRequest of an OpenAI ``/v1/chat/completions`` body.  A [system?, user] chat keeps the
     reference's request shape (same prompt rendering and seed as the in-process provider)."""
@@ -174,7 +205,7 @@ def openai_request(body: Dict[str, Any], default_temp: float = 1.0, vocab: Optio
             raise BadRequest("unsupported message role %r" % role)
         turns.append({"role": role, "content": _text(m.get("content", ""))})
     max_tokens, temp = _common(body, default_temp)
-    filters = {**_filters(body), **_penalties(body), **_constraints(body, max_tokens, vocab)}
+    filters = {**_filters(body), **_penalties(body), **_constraints(body, max_tokens, vocab), **_logprob_fields(body)}
     roles = [t["role"] for t in turns]
     if roles in (["user"], ["system", "user"]):
         return GenRequest(user=turns[-1]["content"], system=turns[0]["content"] if len(turns) == 2 else None,
@@ -197,6 +228,8 @@ def anthropic_request(body: Dict[str, Any], default_temp: float = 1.0, vocab: Op
             raise BadRequest("unsupported message role %r" % role)
         turns.append({"role": role, "content": _text(m.get("content", ""))})
     max_tokens, temp = _common(body, default_temp)
+    if body.get("logprobs") is not None or body.get("top_logprobs") is not None:
+        raise BadRequest("the messages API has no logprobs field: use /v1/chat/completions")
     filters = {**_filters(body), **_penalties(body), **_constraints(body, max_tokens, vocab)}
     if [t["role"] for t in turns[-1:]] != ["user"]:
         raise BadRequest("the last message must be from the user")
@@ -211,11 +244,31 @@ def _finish(res: GenResult) -> str:
     return "length" if (res.extra or {}).get("finish_reason") == "length" else "stop"
 
 
-def openai_response(res: GenResult, model: str) -> Dict[str, Any]:
+def openai_logprobs(rec: Dict[str, Any], tokenizer=None) -> Dict[str, Any]:
+    """``choices[0].logprobs`` of a GenResult.extra["logprobs"] record: one {token, logprob, bytes,
+    top_logprobs: [{token, logprob, bytes}]} per generated token, special tokens spelled out; a non-finite
+    log-probability is sent as -9999.0."""
+    import math
+
+    def entry(tok: int, lp: float) -> Dict[str, Any]:
+        raw = tokenizer.decode_bytes([tok], skip_special=False) if tokenizer is not None else b""
+        return {"token": raw.decode("utf-8", errors="replace"),
+                "logprob": float(lp) if math.isfinite(lp) else NO_LOGPROB, "bytes": list(raw)}
+
+    tops = rec.get("top") or [[] for _ in rec["token_ids"]]
+    return {"content": [dict(entry(t, lp), top_logprobs=[entry(int(a), float(b)) for a, b in top])
+                        for t, lp, top in zip(rec["token_ids"], rec["token_logprobs"], tops)]}
+
+
+def openai_response(res: GenResult, model: str, tokenizer=None) -> Dict[str, Any]:
+    choice: Dict[str, Any] = {"index": 0, "message": {"role": "assistant", "content": res.text},
+                              "finish_reason": _finish(res)}
+    rec = (res.extra or {}).get("logprobs")
+    if rec is not None:  # only a request that asked carries the key
+        choice["logprobs"] = openai_logprobs(rec, tokenizer)
     return {"id": "chatcmpl-" + uuid.uuid4().hex[:24], "object": "chat.completion", "created": int(time.time()),
             "model": model,
-            "choices": [{"index": 0, "message": {"role": "assistant", "content": res.text},
-                         "finish_reason": _finish(res)}],
+            "choices": [choice],
             "usage": {"prompt_tokens": res.prompt_tokens, "completion_tokens": res.completion_tokens,
                       "total_tokens": res.prompt_tokens + res.completion_tokens}}
 
@@ -364,7 +417,7 @@ class ContinuousBatcher(Batcher):
             return
 
     def loop(self) -> None:
-        from .engine.provider import sampling_params
+        from .engine.provider import logprobs_record, sampling_params
         prov = self.provider
         while not self.stop.is_set():
             items = self._collect(0.1)
@@ -420,8 +473,11 @@ class ContinuousBatcher(Batcher):
                         push(rid, text, True)
                         sent.pop(rid)
                     req, lp, fut = pending.pop(rid)[:3]
-                    self._resolve(lp, fut, GenResult(text, o.prompt_len, len(o.token_ids),
-                                                     extra={"finish_reason": o.finish_reason}))
+                    extra = {"finish_reason": o.finish_reason}
+                    rec = logprobs_record(o).get("lp")
+                    if rec is not None:
+                        extra["logprobs"] = rec
+                    self._resolve(lp, fut, GenResult(text, o.prompt_len, len(o.token_ids), extra=extra))
 
             def feeder(done):
                 finish(done)
@@ -529,6 +585,7 @@ def build_app(batcher: Batcher, model_name: str, api_key: Optional[str] = None, 
     # checked against it here, so a bad id is this client's 400
     model_config = getattr(getattr(batcher, "provider", None), "model_config", None)
     vocab = getattr(model_config(), "vocab_size", None) if callable(model_config) else None
+    tokenizer = getattr(getattr(batcher, "provider", None), "tokenizer", None)  # spells out logprobs tokens
 
     async def _serve(request: Request, parse, render):
         if not _authorised(request):
@@ -546,7 +603,7 @@ def build_app(batcher: Batcher, model_name: str, api_key: Optional[str] = None, 
         res = await batcher.submit(req)
         if res.error:
             return _err(500, res.error, "engine_error")
-        out = render(res, model)
+        out = render(res, model, tokenizer) if render is openai_response else render(res, model)
         if body.get("stream"):  # Anthropic: the whole message as one event
             async def events():
                 yield "data: %s\n\n" % json.dumps(out)

@@ -24,6 +24,14 @@ entries (a quarter of them bans) and a minimum length that suppresses its armed 
 same launch over rows with nothing to do (every workgroup exits at once).
 
     python tools/bench_sampler.py --constraints --bs 1,10,39 > profiles/sampler_constraints.jsonl
+
+``--logprobs``: the cost of the two launches a logprob decode step adds -- ops.hip.logprobs (segments + merge)
+before the sampler and ops.hip.logprobs_pick after it -- for every row asking with a top list of ``n`` entries,
+next to the plain sampler launch timed in the same run: ``logprobs_us`` = (rewrite + logprobs) - rewrite,
+``plain_us`` = (rewrite + sample) - rewrite, ``pick_us`` = (rewrite + sample + pick) - (rewrite + sample),
+``off_us`` = the logprobs launch over rows that do not ask (every workgroup exits at once).
+
+    python tools/bench_sampler.py --logprobs --bs 1,10,39 > profiles/sampler_logprobs.jsonl
 """
 import argparse
 import json
@@ -43,6 +51,8 @@ ap.add_argument("--penalties", action="store_true", help="time the penalize laun
 ap.add_argument("--gen-counts", default="1,256,2048", help="--penalties: generated tokens per row")
 ap.add_argument("--constraints", action="store_true", help="time the constrain launch instead of the filter")
 ap.add_argument("--entries", default="1,300", help="--constraints: logit-bias entries per row")
+ap.add_argument("--logprobs", action="store_true", help="time the logprobs launches instead of the filter")
+ap.add_argument("--top-ns", default="0,5,20", help="--logprobs: top-list entries per row")
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.tree))
 
@@ -144,6 +154,51 @@ for B in (int(b) for b in args.bs.split(",")):
                 d = [timed(step, args.iters) - timed(rewrite, args.iters) for _ in range(args.repeats)]
                 rec["%s_us" % mode] = round(statistics.median(d), 2)
                 rec["%s_us_min_max" % mode] = [round(min(d), 2), round(max(d), 2)]
+            print(json.dumps(rec), flush=True)
+        continue
+
+    if args.logprobs:
+        from llm_map_reduce_summarizer_amd import ops
+        for n in (int(x) for x in args.top_ns.split(",")):
+            st = State(B, args.iters + 8, [0] * B, [1.0] * B)
+            st.lp = ops.LogprobStore(B, args.iters + 8, dev)
+            rec = {"B": B, "V": args.vocab, "top_n": n, "iters": args.iters, "repeats": args.repeats}
+
+            def lp_only(i, st=st):
+                rewrite(i)
+                hip.logprobs(logits, st)
+
+            def sample_only(i, st=st):
+                rewrite(i)
+                hip.sample(logits, st)
+
+            def sample_pick(i, st=st):
+                rewrite(i)
+                hip.sample(logits, st)
+                hip.logprobs_pick(logits, st)
+
+            def loop(fn, st=st):
+                st.gen_count.zero_()  # the sampler advances it: every timed loop starts at record 0
+                st.done.zero_()
+                return timed(fn, args.iters)
+
+            for mode, lp_n in (("logprobs", n), ("off", -1)):
+                st.lp_n = torch.full((B,), lp_n, dtype=torch.int32, device=dev)
+                loop(lp_only)
+                d = [loop(lp_only) - timed(rewrite, args.iters) for _ in range(args.repeats)]
+                rec["%s_us" % mode] = round(statistics.median(d), 2)
+                rec["%s_us_min_max" % mode] = [round(min(d), 2), round(max(d), 2)]
+            st.lp_n = torch.full((B,), n, dtype=torch.int32, device=dev)
+            loop(lp_only)  # a slot for the pick (lp_slot 0: the sampler's first record of every loop)
+            loop(sample_pick)
+            plain, pick = [], []
+            for _ in range(args.repeats):
+                a, b, c = loop(sample_pick), loop(sample_only), timed(rewrite, args.iters)
+                plain.append(b - c)
+                pick.append(a - b)
+            for name, d in (("plain", plain), ("pick", pick)):
+                rec["%s_us" % name] = round(statistics.median(d), 2)
+                rec["%s_us_min_max" % name] = [round(min(d), 2), round(max(d), 2)]
             print(json.dumps(rec), flush=True)
         continue
 
