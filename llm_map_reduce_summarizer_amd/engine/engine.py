@@ -27,7 +27,7 @@ import os
 import time
 from dataclasses import dataclass, field, replace
 from types import SimpleNamespace
-from typing import Dict, List, Mapping, Optional, Sequence, Tuple, Union
+from typing import Dict, List, Mapping, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -51,24 +51,35 @@ def _always() -> bool:
     return True
 
 
-def _any_filtered(seqs) -> bool:
-    """Whether any of these sequences samples through a top-k / top-p filter (host-side: _Seq.params)."""
-    return any(s.params.filtered for s in seqs)
+class SamplerMode(NamedTuple):
+    """What the sampler of one batch has to do beyond plain sampling; a flag is set when ANY row of the batch
+    needs it (host-side: _Seq.params).  It picks the launches of ``LLMEngine._sample`` and the decode graph."""
+    filtered: bool = False  # a row samples through a top-k / top-p filter
+    penalised: bool = False  # a row carries a repetition / frequency / presence penalty
+    constrained: bool = False  # a row carries a logit bias, a minimum length or stop ids of its own
+    logprobs: bool = False  # a row asks for the log-probabilities of its tokens
 
+    # flag -> the stats counter of the steps that ran with it (LLMEngine._count)
+    STATS = (("filtered", "filtered_steps"), ("penalised", "penalised_steps"),
+             ("constrained", "constrained_steps"), ("logprobs", "logprob_steps"))
 
-def _any_penalised(seqs) -> bool:
-    """Whether any of these sequences carries a repetition / frequency / presence penalty."""
-    return any(s.params.penalised for s in seqs)
+    @classmethod
+    def of(cls, seqs) -> "SamplerMode":
+        f = p = c = lp = False
+        for s in seqs:
+            sp = s.params
+            f, p, c, lp = f or sp.filtered, p or sp.penalised, c or sp.constrained, lp or sp.logprobs
+        return cls(bool(f), bool(p), bool(c), bool(lp))
 
+    @property
+    def whole(self) -> bool:
+        """Whether the batch needs whole logit rows (the filter and the logprobs kernels take them): gathered
+        over the TP group on a vocab-parallel engine, whose decode steps then run eagerly."""
+        return self.filtered or self.logprobs
 
-def _any_constrained(seqs) -> bool:
-    """Whether any of these sequences carries a logit bias, a minimum length or stop ids of its own."""
-    return any(s.params.constrained for s in seqs)
-
-
-def _any_logprobs(seqs) -> bool:
-    """Whether any of these sequences asks for the log-probabilities of its tokens."""
-    return any(s.params.logprobs for s in seqs)
+    def first(self) -> "SamplerMode":
+        """Mode of a first-token sample: gen_count is 0, so there is no generated token to penalise."""
+        return self._replace(penalised=False)
 
 
 @dataclass
@@ -271,7 +282,9 @@ class DecodeState:
                    "temps", "seeds", "top_k", "top_p", "thresh", "rep_pen", "freq_pen", "pres_pen",
                    "bias_tok", "bias_val", "bias_n", "min_new", "stop_ids", "lp_n")
 
-    def view(self, start: int, n: int) -> "DecodeState":
+    def view(self, start: int, n: int, mode: SamplerMode = SamplerMode()) -> "DecodeState":
+        """Rows [start, start + n) as a state of their own; ``mode`` (default: plain) becomes the view's
+        ``filtered`` / ``penalised`` / ``constrained`` / ``logprobs`` attributes, which the sampler reads."""
         v = object.__new__(DecodeState)
         v.max_seqs = n
         for f in self._ROW_FIELDS:
@@ -280,10 +293,7 @@ class DecodeState:
         v.eos, v.eos_ids = self.eos, self.eos_ids
         v.filter_ws = self.filter_ws
         v.lp = self.lp.view(start, n)
-        v.logprobs = False  # set by the engine on the view of a batch with a row that asks for logprobs
-        v.filtered = False  # set by the engine on the view of a batch with a top-k / top-p row
-        v.penalised = False  # ... and of a batch with a penalised row
-        v.constrained = False  # ... and of a batch with a constrained row (bias / min_new / stop_ids)
+        v.filtered, v.penalised, v.constrained, v.logprobs = mode
         return v
 
     def move_row(self, src: int, dst: int, records: bool = True) -> None:
@@ -441,8 +451,8 @@ class LLMEngine:
             log.warning("TP=%d without the custom all-reduce: decode hipGraphs disabled", self.model.tp_size)
             self.use_graphs = False
         # decode graphs / attention workspaces per (batch bucket, context class): the attention's split
-        # plan depends on how long the contexts get (ops.hip.decode_attn_plan); a graph whose sampler runs
-        # the top-k / top-p filter has its own key (_graph_key)
+        # plan depends on how long the contexts get (ops.hip.decode_attn_plan); every sampler mode other than
+        # the plain one has graphs of its own, whose keys carry its flags (_graph_key)
         self._graphs: Dict[tuple, "torch.cuda.CUDAGraph"] = {}
         self._ctx_cls = 0
         self._on_prefill = None
@@ -563,27 +573,24 @@ class LLMEngine:
         """Sample every sequence's first generated token from its prompt's last row (fed position
         prompt_len - 1); ``seqs`` occupy consecutive slots.  ``logits`` come from a forward with
         ``gather=self._gather(seqs)``."""
-        st = self.state
-        v = st.view(seqs[0].slot, len(seqs))
+        # the first token is filtered and constrained like every other, and has a log-probability record
+        mode = SamplerMode.of(seqs).first()
+        v = self.state.view(seqs[0].slot, len(seqs), mode)
         v.positions.copy_(torch.tensor([len(s.prompt) - 1 for s in seqs], dtype=torch.int32).to(
             self.device, non_blocking=True))
-        filtered = _any_filtered(seqs)
-        if filtered:
-            self.stats["filtered_steps"] += 1  # the first token is filtered like every other
-        v.filtered = filtered
-        v.constrained = _any_constrained(seqs)  # gen_count is 0: the first token is constrained like any other
-        if v.constrained:
-            self.stats["constrained_steps"] += 1
-        v.logprobs = _any_logprobs(seqs)  # token 0 has a record like every other
-        if v.logprobs:
-            self.stats["logprob_steps"] += 1
+        self._count(mode, 1)
         self._sample(logits, v)
+
+    def _count(self, mode: SamplerMode, steps: int) -> None:
+        """Count ``steps`` sampler steps in ``mode`` into the stats."""
+        for flag, key in SamplerMode.STATS:
+            if getattr(mode, flag):
+                self.stats[key] += steps
 
     def _gather(self, seqs: Sequence[_Seq]) -> bool:
         """Whether the forward that feeds these sequences' sampler gathers the logits over the TP group: always
-        without vocab-parallel sampling, and for a filtered batch or one with a row that asks for logprobs
-        (the filter and the logprobs kernels take whole rows)."""
-        return not self.model.tp_sampling or _any_filtered(seqs) or _any_logprobs(seqs)
+        without vocab-parallel sampling, and for a batch that needs whole rows (SamplerMode.whole)."""
+        return not self.model.tp_sampling or SamplerMode.of(seqs).whole
 
     def _prefill_pass(self, seqs: List[_Seq], spans, paged: bool, final: bool = True) -> None:
         """One packed forward over prompt slices ``spans`` [(start, end)] of ``seqs``; on the final pass,
@@ -598,89 +605,70 @@ class LLMEngine:
 
     # ------------------------------------------------------------------ decode
     def _sample(self, logits: torch.Tensor, st_view) -> None:
-        """``st_view.filtered``: some row has a top-k / top-p filter.  Such a batch samples from whole rows
-        (gathered on a vocab-parallel engine) with the single-GPU filtered sampler, the same on every rank.
-        ``st_view.penalised``: some row has a repetition / frequency / presence penalty; the logits of the
-        tokens it generated are rewritten first -- whole rows, or on the vocab-parallel path this rank's
-        shard (every rank holds the same out_tokens).
-        ``st_view.constrained``: some row has a logit bias, a minimum length or stop ids of its own; the
-        logits are constrained before anything else, on the same columns as the penalties, and the sampler
-        ends in the finish that honours the rows' stop ids.
-        ``st_view.logprobs``: some row asks for log-probabilities; they are taken from the whole rows (gathered
-        on a vocab-parallel engine, as for a filter) once constrained and penalised, before the sampler, and
-        the sampled token's is picked after it."""
-        whole = st_view.filtered or st_view.logprobs
-        shard = self.model.tp_sampling and not whole
-        if st_view.constrained:
+        """Sample one token per row of ``st_view`` in the view's sampler mode (SamplerMode: its four attributes),
+        in this order.  Constrained: the logits are constrained before anything else, and the sampler ends in
+        the finish that honours the rows' stop ids.  Penalised: the logits of the tokens a row generated are
+        rewritten.  Both work on whole rows, or on the vocab-parallel path on this rank's shard (every rank
+        holds the same out_tokens).  Logprobs: taken from the rows once constrained and penalised, before the
+        sampler, and the sampled token's is picked after it.  Filtered: the single-GPU filtered sampler.  A
+        filtered or logprobs batch works on whole rows (gathered on a vocab-parallel engine), the same on
+        every rank."""
+        mode = SamplerMode(st_view.filtered, st_view.penalised, st_view.constrained, st_view.logprobs)
+        shard = self.model.tp_sampling and not mode.whole
+        if mode.constrained:
             ops.constrain(logits, st_view, self.model.vocab_offset if shard else 0)
-        if st_view.penalised:
+        if mode.penalised:
             ops.penalize(logits, st_view, self.model.vocab_offset if shard else 0)
-        if st_view.logprobs:
+        if mode.logprobs:
             ops.logprobs(logits, st_view)
-        if st_view.filtered:
+        if mode.filtered:
             ops.sample(logits, st_view, filtered=True)
         elif shard:  # local vocab shard + cross-rank max of the 8-byte Gumbel keys
             ops.sample_tp(logits, st_view, self.model.vocab_offset, self.model.custom_ar.max_u64_)
         else:
             ops.sample(logits, st_view)
-        if st_view.logprobs:
+        if mode.logprobs:
             ops.logprobs_pick(logits, st_view)
 
-    def _decode_once(self, B: int, filtered: bool = False, penalised: bool = False,
-                     constrained: bool = False, logprobs: bool = False) -> None:
+    def _decode_once(self, B: int, mode: SamplerMode) -> None:
         st = self.state
         logits = self.model.decode(st.next_ids[:B], st.positions[:B], st.seq_idx[:B], st.block_tables[:B],
                                    self.kv.k, self.kv.v, workspace=self._workspace(B),
-                                   gather=filtered or logprobs or not self.model.tp_sampling)
-        v = st.view(0, B)
-        v.filtered = filtered
-        v.penalised = penalised
-        v.constrained = constrained
-        v.logprobs = logprobs
-        self._sample(logits, v)
+                                   gather=mode.whole or not self.model.tp_sampling)
+        self._sample(logits, st.view(0, B, mode))
 
-    def _decode_steps(self, B: int, steps: int, filtered: bool = False, penalised: bool = False,
-                      constrained: bool = False, logprobs: bool = False) -> None:
-        if filtered:
-            self.stats["filtered_steps"] += steps
-        if penalised:
-            self.stats["penalised_steps"] += steps
-        if constrained:
-            self.stats["constrained_steps"] += steps
-        if logprobs:
-            self.stats["logprob_steps"] += steps
+    def _decode_steps(self, B: int, steps: int, mode: SamplerMode) -> None:
+        self._count(mode, steps)
         if self._fault_delay is not None and int(self._fault_delay[0]) == self.model.tp_rank \
                 and self.model.custom_ar is not None:
             delay, self._fault_delay = self._fault_delay[1], None  # once
             log.warning("fault injection: TP rank %d sleeps %.1f s before a decode window", self.model.tp_rank, delay)
             time.sleep(delay)
-        if not self.use_graphs or ((filtered or logprobs) and self.model.tp_sampling):
-            # a filtered or logprob step of a vocab-parallel engine gathers the logits on RCCL, which stays
-            # outside any capture: it runs eagerly
+        if not self.use_graphs or (mode.whole and self.model.tp_sampling):
+            # a whole-row step of a vocab-parallel engine gathers the logits on RCCL, which stays outside any
+            # capture: it runs eagerly
             for _ in range(steps):
-                self._decode_once(B, filtered, penalised, constrained, logprobs)
+                self._decode_once(B, mode)
             return
-        g = self._graphs.get(self._graph_key(B, filtered, penalised, constrained, logprobs))
+        g = self._graphs.get(self._graph_key(B, mode))
         if g is None:
-            g = self._capture(B, filtered, penalised, constrained, logprobs)
+            g = self._capture(B, mode)
         for _ in range(steps):
             g.replay()
 
-    def _graph_key(self, B: int, filtered: bool, penalised: bool = False, constrained: bool = False,
-                   logprobs: bool = False) -> tuple:
-        """Key of a decode graph: (bucket, context class), (bucket, context class, True) for the graph
-        whose sampler filters, (bucket, context class, filtered, "pen") for the graphs that penalise
-        first, and (bucket, context class, filtered, penalised, "con") for the graphs that constrain before
-        all that and finish with the rows' stop ids; the graphs that also take log-probabilities carry all
-        three flags and a trailing "lp" (all but the plain ones captured on first use; ``capture_graphs``
-        captures the plain ones)."""
-        if logprobs:
-            return (B, self._ctx_cls, filtered, penalised, constrained, "lp")
-        if constrained:
-            return (B, self._ctx_cls, filtered, penalised, "con")
-        if penalised:
-            return (B, self._ctx_cls, filtered, "pen")
-        return (B, self._ctx_cls, True) if filtered else (B, self._ctx_cls)
+    def _graph_key(self, B: int, mode: SamplerMode) -> tuple:
+        """Key of the decode graph of ``mode``: (bucket, context class) and the mode's flags up to the last
+        one set, named by a trailing tag from the second on -- (B, cls), (B, cls, True), (B, cls, filtered,
+        "pen"), (B, cls, filtered, penalised, "con"), (B, cls, filtered, penalised, constrained, "lp").  All
+        but the plain graphs are captured on first use; ``capture_graphs`` captures the plain ones."""
+        base = (B, self._ctx_cls)
+        if mode.logprobs:
+            return base + (mode.filtered, mode.penalised, mode.constrained, "lp")
+        if mode.constrained:
+            return base + (mode.filtered, mode.penalised, "con")
+        if mode.penalised:
+            return base + (mode.filtered, "pen")
+        return base + (True,) if mode.filtered else base
 
     def capture_graphs(self, max_batch: Optional[int] = None) -> int:
         """Capture the decode hipGraph of every batch bucket up to ``max_batch`` now (engine start-up,
@@ -706,8 +694,7 @@ class LLMEngine:
         self._sync()
         return n
 
-    def _capture(self, B: int, filtered: bool = False, penalised: bool = False, constrained: bool = False,
-                 logprobs: bool = False):
+    def _capture(self, B: int, mode: SamplerMode = SamplerMode()):
         # snapshot state rows the warm-up step will advance, run it eagerly once (lazy kernel-library
         # load, workspace and split-K ticket allocation), restore, then capture.
         st = self.state
@@ -717,17 +704,17 @@ class LLMEngine:
         with torch.cuda.stream(s):
             # (a filtered warm-up also allocates the filter workspace, a logprob one the record store; the
             # record it writes is the one the first replayed step writes again)
-            self._decode_once(B, filtered, penalised, constrained, logprobs)
+            self._decode_once(B, mode)
         torch.cuda.current_stream(self.device).wait_stream(s)
         for f, t in snap.items():
             getattr(st, f)[:B].copy_(t)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._decode_once(B, filtered, penalised, constrained, logprobs)
+            self._decode_once(B, mode)
         # capture does not execute; restore anyway in case the backend ran the work
         for f, t in snap.items():
             getattr(st, f)[:B].copy_(t)
-        self._graphs[self._graph_key(B, filtered, penalised, constrained, logprobs)] = g
+        self._graphs[self._graph_key(B, mode)] = g
         self.stats["graph_captures"] += 1
         return g
 
@@ -760,7 +747,7 @@ class LLMEngine:
         eos = list(self.state.eos_ids)
         if ignore_eos:  # device-side stop set: captured graphs see it at replay (sampler.hip EOS_SLOTS)
             self.state.set_eos([])
-        self._ignore_eos = bool(ignore_eos)  # ... and the rows' own stop ids are written as -1s (_set_constraints)
+        self._ignore_eos = bool(ignore_eos)  # ... and the rows' own stop ids are written as -1s (_setup_slot)
         try:
             ar = self.model.custom_ar
             failed: Optional[BaseException] = None
@@ -901,8 +888,7 @@ class LLMEngine:
                 t0 = time.perf_counter()
                 if t_window_end is not None:  # host work + prefill between two windows of running rows
                     self.stats["max_window_gap_s"] = max(self.stats.get("max_window_gap_s", 0.0), t0 - t_window_end)
-                self._decode_steps(B, steps, _any_filtered(active), _any_penalised(active),
-                                   _any_constrained(active), _any_logprobs(active))
+                self._decode_steps(B, steps, SamplerMode.of(active))
                 self._sync()
                 t_window_end = time.perf_counter()
                 self.stats["decode_s"] += t_window_end - t0
@@ -971,7 +957,6 @@ class LLMEngine:
         ``max_prefill_tokens``.  The batches are enqueued back to back and the device is synchronised once,
         after the last: the host assembles batch k+1 while batch k runs (a sync per batch idled the GPU for
         that assembly, ~3-5 ms per 16k-token pass)."""
-        st = self.state
         batch: List[_Seq] = []
         tokens = 0
         t0 = time.perf_counter()
@@ -990,20 +975,7 @@ class LLMEngine:
             waiting.pop(0)
             s.pages = self.kv.alloc.alloc(need)
             s.slot = len(active) + len(batch)
-            row = torch.zeros(self.max_pages, dtype=torch.int32)
-            row[:need] = torch.tensor(s.pages, dtype=torch.int32)
-            st.block_tables[s.slot].copy_(row.to(self.device, non_blocking=True))
-            st.max_new[s.slot] = s.params.max_new_tokens
-            st.gen_count[s.slot] = 0
-            st.done[s.slot] = 0
-            st.temps[s.slot] = float(s.params.temperature)
-            st.seeds[s.slot] = int(s.params.seed)
-            st.top_k[s.slot] = min(int(s.params.top_k), _I32_MAX)
-            st.top_p[s.slot] = float(s.params.top_p)
-            self._set_penalties(s.slot, s.params)
-            self._set_constraints(s.slot, s.params)
-            self._set_logprobs(s.slot, s.params)
-            st.result[s.slot] = 0
+            self._setup_slot(s, self._page_row(s.pages))
             if s.imported is not None:  # no forward pass: KV + first token come from elsewhere
                 self._install(s)
                 active.append(s)
@@ -1031,7 +1003,6 @@ class LLMEngine:
         """Reserve pages (and a prefill-table row) for waiting requests while a batch decodes; their
         forward passes run slice by slice in ``_interleaved_pass``.  Imported prefills need no forward:
         they are installed into a decode slot at once."""
-        st = self.state
         used = {s.pf_slot for s in prefilling}
         while waiting and len(active) + len(prefilling) < self.max_num_seqs:
             s = waiting[0]
@@ -1040,8 +1011,7 @@ class LLMEngine:
                 break
             waiting.pop(0)
             s.pages = self.kv.alloc.alloc(need)
-            row = torch.zeros(self.max_pages, dtype=torch.int32)
-            row[:need] = torch.tensor(s.pages, dtype=torch.int32)
+            row = self._page_row(s.pages)
             if s.imported is not None:
                 s.slot = len(active)
                 self._setup_slot(s, row)
@@ -1055,43 +1025,39 @@ class LLMEngine:
             prefilling.append(s)
             self.stats["interleaved_prefills"] = self.stats.get("interleaved_prefills", 0) + 1
 
-    def _set_penalties(self, slot: int, params: SamplingParams) -> None:
-        st = self.state
-        st.rep_pen[slot] = float(params.repetition_penalty)
-        st.freq_pen[slot] = float(params.frequency_penalty)
-        st.pres_pen[slot] = float(params.presence_penalty)
-
-    def _set_constraints(self, slot: int, params: SamplingParams) -> None:
-        """Constraint rows of ``slot``.  Under ``generate(ignore_eos=True)`` the row's stop ids are written as
-        -1s, as the engine's own are: pinned work stays pinned (and min_tokens has nothing to suppress)."""
-        st = self.state
-        items = params.bias_items()
-        st.bias_n[slot] = len(items)
-        if items:
-            st.bias_tok[slot, :len(items)].copy_(torch.tensor([int(t) for t, _ in items], dtype=torch.int32))
-            st.bias_val[slot, :len(items)].copy_(torch.tensor([float(x) for _, x in items], dtype=torch.float32))
-        st.min_new[slot] = int(params.min_tokens)
-        stops = [] if self._ignore_eos else [int(t) for t in params.stop_token_ids]
-        st.stop_ids[slot].copy_(torch.tensor(stops + [-1] * (MAX_STOP_IDS - len(stops)), dtype=torch.int32))
-
-    def _set_logprobs(self, slot: int, params: SamplingParams) -> None:
-        self.state.lp_n[slot] = int(params.top_logprobs) if params.logprobs else -1
+    def _page_row(self, pages: List[int]) -> torch.Tensor:
+        """Page-table row (host) of a sequence that holds ``pages``; the entries past them -> scratch page 0."""
+        row = torch.zeros(self.max_pages, dtype=torch.int32)
+        row[:len(pages)] = torch.tensor(pages, dtype=torch.int32)
+        return row
 
     def _setup_slot(self, s: _Seq, row: torch.Tensor) -> None:
-        """Decode-state row of ``s`` at ``s.slot``: its pages, budget and sampling parameters."""
-        st = self.state
-        st.block_tables[s.slot].copy_(row.to(self.device, non_blocking=True))
-        st.max_new[s.slot] = s.params.max_new_tokens
-        st.gen_count[s.slot] = 0
-        st.done[s.slot] = 0
-        st.temps[s.slot] = float(s.params.temperature)
-        st.seeds[s.slot] = int(s.params.seed)
-        st.top_k[s.slot] = min(int(s.params.top_k), _I32_MAX)
-        st.top_p[s.slot] = float(s.params.top_p)
-        self._set_penalties(s.slot, s.params)
-        self._set_constraints(s.slot, s.params)
-        self._set_logprobs(s.slot, s.params)
-        st.result[s.slot] = 0
+        """Decode-state row of ``s`` at ``s.slot``: its pages (``row``: _page_row, or a device row that holds
+        them already), budget and sampling parameters -- the only writer of a slot's parameter rows.  Under
+        ``generate(ignore_eos=True)`` the row's stop ids are written as -1s, as the engine's own are: pinned
+        work stays pinned (and min_tokens has nothing to suppress)."""
+        st, i, sp = self.state, s.slot, s.params
+        st.block_tables[i].copy_(row.to(self.device, non_blocking=True))
+        st.max_new[i] = sp.max_new_tokens
+        st.gen_count[i] = 0
+        st.done[i] = 0
+        st.temps[i] = float(sp.temperature)
+        st.seeds[i] = int(sp.seed)
+        st.top_k[i] = min(int(sp.top_k), _I32_MAX)
+        st.top_p[i] = float(sp.top_p)
+        st.rep_pen[i] = float(sp.repetition_penalty)
+        st.freq_pen[i] = float(sp.frequency_penalty)
+        st.pres_pen[i] = float(sp.presence_penalty)
+        items = sp.bias_items()
+        st.bias_n[i] = len(items)
+        if items:
+            st.bias_tok[i, :len(items)].copy_(torch.tensor([int(t) for t, _ in items], dtype=torch.int32))
+            st.bias_val[i, :len(items)].copy_(torch.tensor([float(x) for _, x in items], dtype=torch.float32))
+        st.min_new[i] = int(sp.min_tokens)
+        stops = [] if self._ignore_eos else [int(t) for t in sp.stop_token_ids]
+        st.stop_ids[i].copy_(torch.tensor(stops + [-1] * (MAX_STOP_IDS - len(stops)), dtype=torch.int32))
+        st.lp_n[i] = int(sp.top_logprobs) if sp.logprobs else -1
+        st.result[i] = 0
 
     def _interleaved_pass(self, prefilling: List[_Seq], active: List[_Seq], max_parts: Optional[int] = None) -> None:
         """One packed forward of the next slices of the prefilling requests (at most ``prefill_chunk``
@@ -1283,15 +1249,7 @@ class LLMEngine:
         s.pages = self.kv.alloc.alloc(need)
         s.slot = 0
         try:
-            row = torch.zeros(self.max_pages, dtype=torch.int32)
-            row[:need] = torch.tensor(s.pages, dtype=torch.int32)
-            st.block_tables[0].copy_(row.to(dev, non_blocking=True))
-            st.max_new[0], st.gen_count[0], st.done[0], st.result[0] = 1, 0, 0, 0
-            st.temps[0], st.seeds[0] = float(params.temperature), int(params.seed)
-            st.top_k[0], st.top_p[0] = min(int(params.top_k), _I32_MAX), float(params.top_p)
-            self._set_penalties(0, params)
-            self._set_constraints(0, s.params)
-            self._set_logprobs(0, s.params)
+            self._setup_slot(s, self._page_row(s.pages))
             slices = self.cp_slices(n, world)
             mine = [(b, e) for b, e in slices[rank] if e > b]
             if len(mine) != len(slices[rank]):  # n >= 2 world: every zigzag chunk holds a token
