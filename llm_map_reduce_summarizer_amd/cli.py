@@ -101,6 +101,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="KV cache format: bf16 (default, $ENGINE_KV_DTYPE); fp8v = V rows as OCP e4m3fn with "
                         "power-of-two row scales, K bf16 (3/4 of the KV bytes per decode step, 8 %% logit error on "
                         "the parity checkpoint; no context-parallel prefill)")
+    e.add_argument("--prefix-cache", action="store_const", const=True, default=None,
+                   help="KV prefix cache ($ENGINE_PREFIX_CACHE=1): a prompt that begins with the tokens of an "
+                        "earlier one takes that prompt's full 64-token KV pages and prefills only the rest "
+                        "(TP=1 engines; off by default)")
     e.add_argument("--no-graphs", action="store_true", help="disable hipGraph capture of decode steps")
     e.add_argument("--max-model-len", type=int, default=None,
                    help="context budget per request (default: 32k for llama3-*, the model window for llama3.1-*); "
@@ -196,6 +200,7 @@ async def async_main(args: argparse.Namespace) -> int:
     if provider == "local":
         popts.update({"dtype": args.dtype, "tp": args.tp, "seed": args.seed, "kv_fraction": args.kv_fraction,
                       "kv_dtype": args.kv_dtype,
+                      "prefix_cache": args.prefix_cache,
                       "use_graphs": not args.no_graphs, "tokenizer": args.tokenizer,
                       "max_num_seqs": args.max_concurrent_requests, "reduce_tp": args.reduce_tp,
                       "parallel": args.parallel,

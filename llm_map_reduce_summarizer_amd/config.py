@@ -87,6 +87,8 @@ class LLMConfig:
         "LOCAL_MODEL": ("llama3-8b", str), "ENGINE_DTYPE": ("bf16", str), "ENGINE_SEED": ("0", int),
         "ENGINE_MAX_NUM_SEQS": ("256", int), "ENGINE_KV_FRACTION": ("0.6", float),
         "ENGINE_KV_DTYPE": ("bf16", str),
+        # KV prefix cache of the local engines: prompts that begin with the same tokens share pages (1 = on)
+        "ENGINE_PREFIX_CACHE": ("0", int),
         "REDUCE_TEMPERATURE": ("0.2", float),
         # sampling filters of the map and the reduce stage (1.0 / 0 = off)
         "TOP_P": ("1.0", float), "TOP_K": ("0", int),

@@ -195,6 +195,8 @@ class GenOutput:
     # top_logprobs most likely (token, log-probability) pairs, most likely first; None unless asked for
     logprobs: Optional[List[float]] = None
     top_logprobs: Optional[List[List[Tuple[int, float]]]] = None
+    # prompt tokens whose K/V came from the prefix cache instead of this request's prefill (whole pages)
+    cached_tokens: int = 0
 
 
 @dataclass
@@ -207,6 +209,8 @@ class _Seq:
     imported: Optional["ImportedPrefill"] = None
     spans: List[Tuple[int, int]] = field(default_factory=list)  # interleaved prefill: slices still to run
     pf_slot: int = -1  # interleaved prefill: row of LLMEngine.pf_tables
+    cached: int = 0  # prefix cache: prompt tokens [0, cached) sit in matched pages, the prefill starts there
+    ids: Optional[np.ndarray] = None  # prefix cache: the prompt as int32 (made once, LLMEngine._ids)
 
 
 @dataclass
@@ -384,8 +388,14 @@ class LLMEngine:
                  max_prefill_tokens: int = 32768, use_graphs: bool = True, sync_every: int = 16,
                  eos_ids: Sequence[int] = (128001, 128009), tp_rank: int = 0, tp_size: int = 1, tp_group=None,
                  weight_dtype: str = "bf16", weights_path: Optional[str] = None, prefill_chunk: int = PREFILL_CHUNK,
-                 kv_dtype: Optional[str] = None):
-        """``kv_dtype``: "bf16" (default, $MRSUM_KV_DTYPE), "fp8v" (V rows fp8, K bf16) or "fp8" -- e4m3fn K/V rows with power-of-two
+                 kv_dtype: Optional[str] = None, prefix_cache: Optional[bool] = None):
+        """``prefix_cache`` (default off, $MRSUM_PREFIX_CACHE=1): keep the full 64-token pages of every prompt
+        this engine prefills findable by their token ids (engine/kv_cache.py PageAllocator), so a later prompt
+        that begins with the same tokens takes those pages into its block table and prefills only the rest
+        through the paged prefill kernel.  Whole pages only, at most (len - 1) // 64 of them; not for imported
+        prefills, the prefill exports or a tensor-parallel engine.
+
+        ``kv_dtype``: "bf16" (default, $MRSUM_KV_DTYPE), "fp8v" (V rows fp8, K bf16) or "fp8" -- e4m3fn K/V rows with power-of-two
         row scales (engine/kv_cache.py): half the KV bytes per decode step; no context-parallel prefill.
 
         ``max_prefill_tokens``: rows of one packed prefill pass (whole prompts up to it; longer prompts are sliced
@@ -462,6 +472,19 @@ class LLMEngine:
                       "filtered_steps": 0, "penalised_steps": 0, "constrained_steps": 0,
                       "logprob_steps": 0}
         self._ignore_eos = False  # set for the length of a generate(ignore_eos=True)
+        if prefix_cache is None:
+            prefix_cache = os.environ.get("MRSUM_PREFIX_CACHE", "0") == "1"
+        if prefix_cache and page_size != self.kv.alloc.PAGE_TOKENS:
+            raise ValueError("the prefix cache needs %d-token pages" % self.kv.alloc.PAGE_TOKENS)
+        if prefix_cache and self.model.tp_size > 1:
+            log.warning("prefix cache: not offered on a tensor-parallel engine (TP=%d), running without it",
+                        self.model.tp_size)
+            prefix_cache = False
+        self.prefix_cache = bool(prefix_cache)
+        self._cache_bypass = False  # set for the length of a prefill export: neither match nor publish
+        self._held: Dict[int, _Seq] = {}  # prefix cache: the sequences of the running generate that hold pages
+        if self.prefix_cache:
+            self.stats.update(prefix_hit_tokens=0, prefix_hit_requests=0, prefix_evictions=0)
 
     # ------------------------------------------------------------------ helpers
     def _bucket(self, n: int) -> int:
@@ -513,10 +536,13 @@ class LLMEngine:
             self.stats["prefill_tokens"] += int(x.ids.numel())
             self._sample_first(seqs, logits)
             return
-        if not chunk or max(len(s.prompt) for s in seqs) <= chunk:
-            self._prefill_pass(seqs, [(0, len(s.prompt)) for s in seqs], paged=self.paged_prefill)
+        # (prefix cache: a sequence's prefill starts at s.cached, its matched pages hold what lies before; the
+        # slices are cut from the remainder, and a pass with such a start reads the prefix through the pages)
+        if not chunk or max(len(s.prompt) - s.cached for s in seqs) <= chunk:
+            self._prefill_pass(seqs, [(s.cached, len(s.prompt)) for s in seqs],
+                               paged=self.paged_prefill or any(s.cached for s in seqs))
             return
-        rounds = max(-(-len(s.prompt) // chunk) for s in seqs)
+        rounds = max(-(-(len(s.prompt) - s.cached) // chunk) for s in seqs)
         passes = []
         for r in range(rounds):
             k = rounds - 1 - r  # slices still to come after this one
@@ -524,9 +550,9 @@ class LLMEngine:
             for s in seqs:
                 n = len(s.prompt)
                 end = n - k * chunk
-                if end > 0:
+                if end > s.cached:
                     part.append(s)
-                    spans.append((max(0, end - chunk), end))
+                    spans.append((max(s.cached, end - chunk), end))
             passes.append((part, spans))
             self.stats["prefill_slices"] = self.stats.get("prefill_slices", 0) + len(part)
         if self.model.tp_size > 1:
@@ -755,6 +781,8 @@ class LLMEngine:
                 out = self._generate(prompts, params, imported or {}, on_prefill, feeder, on_sync)
             except Exception as e:  # noqa: BLE001 -- re-raised below, after the group's vote
                 failed = e
+                if self.prefix_cache:
+                    self._drop_held()
             if ar is not None:
                 # every TP rank votes whatever happened locally, so the group's collective sequence stays
                 # aligned: a local exception fails the call on every rank; a timed-out P2P wait anywhere
@@ -829,6 +857,7 @@ class LLMEngine:
     def _generate(self, prompts: Sequence[Sequence[int]], params: Sequence[SamplingParams],
                   imported: Dict[int, ImportedPrefill], on_prefill, feeder=None, on_sync=None) -> List[GenOutput]:
         self.stats["generate_calls"] += 1
+        self._held.clear()
         self._on_prefill = on_prefill
         results: List[Optional[GenOutput]] = [None] * len(prompts)
         finished: List[int] = []  # request indices done since the last feeder call
@@ -906,13 +935,14 @@ class LLMEngine:
                     g = int(gen[i])
                     ids = toks[i, :g].tolist()
                     reason = "length" if g >= s.params.max_new_tokens else "stop"
-                    results[s.rid] = GenOutput(ids, len(s.prompt), reason)
+                    results[s.rid] = GenOutput(ids, len(s.prompt), reason, cached_tokens=s.cached)
                     if s.params.logprobs:
                         results[s.rid].logprobs, results[s.rid].top_logprobs = st.lp.read(
                             i, g, s.params.top_logprobs)
                     finished.append(s.rid)
                     self.stats["decode_tokens"] += g
-                    self.kv.alloc.free(s.pages)
+                    self.kv.alloc.release(s.pages)
+                    self._held.pop(s.rid, None)
                 self._compact(active, set(fin))
                 if not active:
                     t_window_end = None
@@ -963,17 +993,23 @@ class LLMEngine:
         ran = False
         while waiting and len(active) + len(batch) < self.max_num_seqs:
             s = waiting[0]
-            need = self.kv.pages_for(len(s.prompt) + s.params.max_new_tokens)
+            hit = self._match(s)
+            need = self.kv.pages_for(len(s.prompt) + s.params.max_new_tokens) - len(hit)
             if need > self.kv.alloc.available():
+                self.kv.alloc.release(hit)
                 break
-            if batch and (s.imported is not None or tokens + len(s.prompt) > self.max_prefill_tokens):
-                # full prefill batch, or an imported prefill (slots stay in admission order): flush
+            if batch and (s.imported is not None or tokens + len(s.prompt) - self.page * len(hit)
+                          > self.max_prefill_tokens or self._pending_shares(s, batch, len(hit))):
+                # full prefill batch, or an imported prefill (slots stay in admission order), or (prefix
+                # cache) the batch is about to write pages this prompt could share -- they become visible
+                # once its passes are enqueued: flush, and admit the request into the next batch
+                self.kv.alloc.release(hit)
                 self._run_prefill(batch, active)
                 ran = True
                 batch, tokens = [], 0
                 continue
             waiting.pop(0)
-            s.pages = self.kv.alloc.alloc(need)
+            self._take_pages(s, hit, need)
             s.slot = len(active) + len(batch)
             self._setup_slot(s, self._page_row(s.pages))
             if s.imported is not None:  # no forward pass: KV + first token come from elsewhere
@@ -981,7 +1017,7 @@ class LLMEngine:
                 active.append(s)
                 continue
             batch.append(s)
-            tokens += len(s.prompt)
+            tokens += len(s.prompt) - s.cached
         if batch:
             self._run_prefill(batch, active)
             ran = True
@@ -990,14 +1026,14 @@ class LLMEngine:
             self.stats["prefill_s"] += time.perf_counter() - t0
         return batch
 
-    def _slices(self, n: int) -> List[Tuple[int, int]]:
-        """Prefill slices of an ``n``-token prompt, aligned to its END exactly as ``_prefill`` cuts them
-        (so an interleaved prefill runs the same slices as a blocking one)."""
+    def _slices(self, n: int, start: int = 0) -> List[Tuple[int, int]]:
+        """Prefill slices of tokens [start, n) of an ``n``-token prompt, aligned to its END exactly as
+        ``_prefill`` cuts them (so an interleaved prefill runs the same slices as a blocking one)."""
         c = self.prefill_chunk
-        if not c or n <= c:
-            return [(0, n)]
-        r = -(-n // c)
-        return [(max(0, n - (k + 1) * c), n - k * c) for k in reversed(range(r))]
+        if not c or n - start <= c:
+            return [(start, n)]
+        r = -(-(n - start) // c)
+        return [(max(start, n - (k + 1) * c), n - k * c) for k in reversed(range(r))]
 
     def _admit_interleaved(self, waiting: List[_Seq], active: List[_Seq], prefilling: List[_Seq]) -> None:
         """Reserve pages (and a prefill-table row) for waiting requests while a batch decodes; their
@@ -1006,11 +1042,13 @@ class LLMEngine:
         used = {s.pf_slot for s in prefilling}
         while waiting and len(active) + len(prefilling) < self.max_num_seqs:
             s = waiting[0]
-            need = self.kv.pages_for(len(s.prompt) + s.params.max_new_tokens)
+            hit = self._match(s)  # (pages another joiner is still writing are not published: not found)
+            need = self.kv.pages_for(len(s.prompt) + s.params.max_new_tokens) - len(hit)
             if need > self.kv.alloc.available():
+                self.kv.alloc.release(hit)
                 break
             waiting.pop(0)
-            s.pages = self.kv.alloc.alloc(need)
+            self._take_pages(s, hit, need)
             row = self._page_row(s.pages)
             if s.imported is not None:
                 s.slot = len(active)
@@ -1021,9 +1059,79 @@ class LLMEngine:
             s.pf_slot = next(i for i in range(self.max_num_seqs) if i not in used)
             used.add(s.pf_slot)
             self.pf_tables[s.pf_slot].copy_(row.to(self.device, non_blocking=True))
-            s.spans = self._slices(len(s.prompt))
+            s.spans = self._slices(len(s.prompt), s.cached)
             prefilling.append(s)
             self.stats["interleaved_prefills"] = self.stats.get("interleaved_prefills", 0) + 1
+
+    # ------------------------------------------------------------------ prefix cache
+    @property
+    def _caching(self) -> bool:
+        return self.prefix_cache and not self._cache_bypass
+
+    def _match(self, s: _Seq) -> List[int]:
+        """Cached pages that hold the head of ``s``'s prompt (a reference taken on each); [] with the cache
+        off and for an imported prefill."""
+        if not self._caching or s.imported is not None:
+            return []
+        return self.kv.alloc.match(self._ids(s))
+
+    @staticmethod
+    def _ids(s: _Seq) -> np.ndarray:
+        if s.ids is None:
+            s.ids = np.asarray(s.prompt, dtype=np.int32)
+        return s.ids
+
+    def _take_pages(self, s: _Seq, hit: List[int], need: int) -> None:
+        """``s`` holds the matched pages ``hit`` followed by ``need`` new ones; its prefill starts after the
+        matched ones."""
+        s.pages = hit + self.kv.alloc.alloc(need)
+        s.cached = self.page * len(hit)
+        if self.prefix_cache:
+            self._held[s.rid] = s
+        if hit:
+            self.stats["prefix_hit_tokens"] += s.cached
+            self.stats["prefix_hit_requests"] += 1
+
+    def _pending_shares(self, s: _Seq, batch: List[_Seq], matched: int) -> bool:
+        """Whether a member of the prefill batch being assembled is about to write a full page that ``s``
+        could share beyond the ``matched`` pages the index gave it (pages of a pending batch are not visible
+        to the index: the request waits for the next batch, where it hits)."""
+        if not self._caching or s.imported is not None:
+            return False
+        P = self.page
+        cap = (len(s.prompt) - 1) // P
+        if cap <= matched:
+            return False
+        a = self._ids(s)
+        for b in batch:
+            m = min(cap, len(b.prompt) // P) * P
+            if m <= matched * P or b.imported is not None:
+                continue
+            o = self._ids(b)
+            if not np.array_equal(a[:P], o[:P]):  # (most pairs part on their first page)
+                continue
+            diff = np.flatnonzero(a[:m] != o[:m])
+            if (int(diff[0]) if diff.size else m) // P > matched:
+                return True
+        return False
+
+    def _publish(self, seqs: Sequence[_Seq]) -> None:
+        """The passes that write ``seqs``' prompt pages are enqueued: their full prompt pages become findable.
+        (A decode step writes position >= len(prompt), past every full prompt page.)"""
+        if self._caching:
+            for s in seqs:
+                self.kv.alloc.publish(self._ids(s), s.pages, len(s.prompt) // self.page)
+
+    def _drop_held(self) -> None:
+        """An exception escaped the generate: give back every page its sequences hold, park their rows and
+        forget every node, so a page whose writing pass failed can never be served."""
+        for s in self._held.values():
+            self.kv.alloc.release(s.pages)
+            s.pages = []
+        self._held.clear()
+        for i in range(self.max_num_seqs):
+            self.state.park_row(i)
+        self.kv.alloc.reset()
 
     def _page_row(self, pages: List[int]) -> torch.Tensor:
         """Page-table row (host) of a sequence that holds ``pages``; the entries past them -> scratch page 0."""
@@ -1107,6 +1215,7 @@ class LLMEngine:
                 active.append(s)
                 prefilling.remove(s)
             self._sample_first(done, logits)
+            self._publish(done)
             if self._on_prefill is not None:
                 self._on_prefill(done)
         self._sync()
@@ -1161,6 +1270,7 @@ class LLMEngine:
 
     def _run_prefill(self, batch: List[_Seq], active: List[_Seq]) -> None:
         self._prefill_isolated(batch)  # enqueued; _admit synchronises once after its last batch
+        self._publish(batch)
         active.extend(batch)
         if self._on_prefill is not None:
             self._on_prefill(batch)
@@ -1191,7 +1301,11 @@ class LLMEngine:
 
         one = [replace(p, max_new_tokens=1, min_tokens=min(p.min_tokens, 1), logprobs=False, top_logprobs=0)
                for p in params]  # (tokens only: a stage that asks for logprobs does not use the hand-off)
-        outs = self.generate(prompts, one, ignore_eos=ignore_eos, on_prefill=grab)
+        self._cache_bypass = True  # the hand-off neither matches nor publishes
+        try:
+            outs = self.generate(prompts, one, ignore_eos=ignore_eos, on_prefill=grab)
+        finally:
+            self._cache_bypass = False
         firsts = [o.token_ids[0] for o in outs]
         packs = [torch.cat([chunks[i][g] for i in range(len(prompts))]) if prompts else
                  torch.empty(0, dtype=self.kv.k.dtype, device=self.device) for g in range(groups)]
@@ -1285,7 +1399,7 @@ class LLMEngine:
             self.stats["prefill_s"] += time.perf_counter() - t0
             return first, kv
         finally:
-            self.kv.alloc.free(s.pages)
+            self.kv.alloc.release(s.pages)
             st.park_row(0)  # slot 0 was borrowed: idle again (stopped, pages -> scratch page 0)
 
     def import_shape(self, prompt_len: int):
@@ -1311,6 +1425,8 @@ class LLMEngine:
         s["decode_tok_s"] = s["decode_tokens"] / s["decode_s"] if s["decode_s"] else 0.0
         s["kv_pages"] = self.kv.num_pages
         s["kv_dtype"] = self.kv.kv_dtype
+        if self.prefix_cache:
+            s["prefix_evictions"] = self.kv.alloc.evictions()
         s["weights_gib"] = self.model.weight_bytes() / 2 ** 30
         if self.device.type == "cuda":
             s["hbm_peak_gib"] = torch.cuda.max_memory_allocated(self.device) / 2 ** 30

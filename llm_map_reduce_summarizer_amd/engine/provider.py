@@ -78,7 +78,8 @@ def sampling_params(req: GenRequest, base_seed: int, config=None):
     top_k, top_p = request_filters(req, config)
     freq, pres, rep = request_penalties(req, config)
     bias, min_tokens, stops = request_constraints(req, config)
-    return SamplingParams(req.max_tokens, req.temperature, _req_seed(base_seed, req), top_k=top_k, top_p=top_p,
+    seed = _req_seed(base_seed, req) + int(getattr(req, "seed_offset", 0) or 0)
+    return SamplingParams(req.max_tokens, req.temperature, seed, top_k=top_k, top_p=top_p,
                           frequency_penalty=freq, presence_penalty=pres, repetition_penalty=rep,
                           logit_bias=bias or None, min_tokens=min_tokens, stop_token_ids=tuple(stops),
                           logprobs=bool(req.logprobs), top_logprobs=int(req.top_logprobs or 0))
@@ -94,10 +95,21 @@ def logprobs_record(o) -> Dict[str, Any]:
                    "top": [[[int(t), float(x)] for t, x in step] for step in (o.top_logprobs or [])]}}
 
 
-def _extra(finish_reason: str, lp: Optional[Dict[str, Any]]) -> Dict[str, Any]:
+def result_record(o) -> Dict[str, Any]:
+    """``logprobs_record`` plus {"cached": GenResult.extra["cached_tokens"]} for an output whose prompt head came
+    from the prefix cache (a plain int; absent when zero)."""
+    rec = logprobs_record(o)
+    if getattr(o, "cached_tokens", 0):
+        rec["cached"] = int(o.cached_tokens)
+    return rec
+
+
+def _extra(finish_reason: str, lp: Optional[Dict[str, Any]], cached: int = 0) -> Dict[str, Any]:
     extra: Dict[str, Any] = {"finish_reason": finish_reason}
     if lp is not None:
         extra["logprobs"] = lp
+    if cached:
+        extra["cached_tokens"] = int(cached)
     return extra
 
 
@@ -147,7 +159,8 @@ class LocalEngineProvider(Provider):
                  kv_fraction: Optional[float] = None, use_graphs: bool = True, max_num_seqs: Optional[int] = None,
                  tokenizer: Optional[str] = None, ignore_eos: bool = False, reduce_tp: Optional[bool] = None,
                  weights: Optional[str] = None, parallel: Optional[str] = None,
-                 fault_inject: Optional[str] = None, kv_dtype: Optional[str] = None, **_ignored):
+                 fault_inject: Optional[str] = None, kv_dtype: Optional[str] = None,
+                 prefix_cache: Optional[bool] = None, **_ignored):
         super().__init__(model, config)
         spec = fault_inject or os.environ.get("MRSUM_FAULT_INJECT", "")
         self._fault_rank, self._fault_left = (int(x) for x in spec.split(":")) if spec else (-1, 0)
@@ -182,6 +195,10 @@ class LocalEngineProvider(Provider):
             # (tests/test_forward_parity_gpu.py), above the 0.15 a variant must meet; fp8v is 8 %
             raise ValueError("kv_dtype must be bf16 or fp8v, got %s" % kv_dtype)
         self._engine_options.setdefault("kv_dtype", kv_dtype)
+        # KV prefix cache of the engines built here (LLMEngine prefix_cache; a TP engine runs without it)
+        if self.config.ENGINE_PREFIX_CACHE if prefix_cache is None else prefix_cache:
+            self._engine_options.setdefault("prefix_cache", True)
+        self.prefix_cache = bool(self._engine_options.get("prefix_cache"))
         if max_num_seqs is not None:
             self._engine_options.setdefault("max_num_seqs", max_num_seqs)
         self.timings: Dict[str, float] = {"generate_s": 0.0, "allgather_s": 0.0}
@@ -225,6 +242,15 @@ class LocalEngineProvider(Provider):
         self.owner_maps: Dict[str, List[List[int]]] = {}  # stage -> replica of every request, per call
         if self.use_tp_engine:
             self._engine_options.setdefault("kv_fraction", float(os.environ.get("MRSUM_DP_KV_FRACTION", "0.5")))
+
+    def prefix_stats(self) -> Dict[str, int]:
+        """The prefix cache's counters of this rank's TP=1 engine ({} with the cache off or no engine yet)."""
+        eng = self._engine
+        if eng is None or not getattr(eng, "prefix_cache", False):
+            return {}
+        return {"prefix_hit_tokens": int(eng.stats["prefix_hit_tokens"]),
+                "prefix_hit_requests": int(eng.stats["prefix_hit_requests"]),
+                "prefix_evictions": int(eng.kv.alloc.evictions())}
 
     def _tp_ok(self, k: int) -> bool:
         """The model shards over TP=k (heads, KV heads, FFN and vocab divisible; at most 8 GPUs)."""
@@ -610,7 +636,7 @@ class LocalEngineProvider(Provider):
                 outs = self.tp_engine_for(k).generate(sub_p, sub_sp, ignore_eos=self.ignore_eos, imported=imported)
                 for i, o in zip(mine, outs):
                     local.append({"i": i, "text": self.tokenizer.decode(o.token_ids), "pt": o.prompt_len,
-                                  "ct": len(o.token_ids), "fr": o.finish_reason, **logprobs_record(o)})
+                                  "ct": len(o.token_ids), "fr": o.finish_reason, **result_record(o)})
             except Exception as e:  # noqa: BLE001 -- SPMD inside the group: its every rank raises alike
                 msg = "rank %d: %s: %s" % (rank, type(e).__name__, e)
                 log.error("TP=%d group %d failed on %d requests: %s", k, rank // k, len(mine), msg)
@@ -650,7 +676,7 @@ class LocalEngineProvider(Provider):
             log.error("TP stage failed: %s", "; ".join(errs))
             return [GenResult("", error="; ".join(errs)) for _ in reqs]
         return [GenResult(self.tokenizer.decode(o.token_ids), o.prompt_len, len(o.token_ids), 0.0,
-                          extra=_extra(o.finish_reason, logprobs_record(o).get("lp"))) for o in outs]
+                          extra=_extra(o.finish_reason, logprobs_record(o).get("lp"), o.cached_tokens)) for o in outs]
 
     async def generate_batch(self, reqs: Sequence[GenRequest]) -> List[GenResult]:
         t0 = time.perf_counter()
@@ -694,7 +720,7 @@ class LocalEngineProvider(Provider):
                     ignore_eos=self.ignore_eos)
                 for i, o in zip(mine, outs):
                     local.append({"i": i, "text": self.tokenizer.decode(o.token_ids), "pt": o.prompt_len,
-                                  "ct": len(o.token_ids), "fr": o.finish_reason, **logprobs_record(o)})
+                                  "ct": len(o.token_ids), "fr": o.finish_reason, **result_record(o)})
             except Exception as e:  # noqa: BLE001 -- never skip the all-gather below: the peers are in it
                 msg = "rank %d: %s: %s" % (self.par.rank, type(e).__name__, e)
                 log.error("engine failed on %d requests: %s", len(mine), msg)
@@ -754,7 +780,7 @@ class LocalEngineProvider(Provider):
 
         def rec(key, idx, o):
             return {key: idx, "text": self.tokenizer.decode(o.token_ids), "pt": o.prompt_len, "ct": len(o.token_ids),
-                    "fr": o.finish_reason, **logprobs_record(o)}
+                    "fr": o.finish_reason, **result_record(o)}
 
         def feeder(done):
             new = []
@@ -831,7 +857,7 @@ def _result(r: Dict[str, Any]) -> GenResult:
     """GenResult of an all-gathered result record ({"text", "pt", "ct", "fr"[, "lp"]} or {"err"})."""
     if "err" in r:
         return GenResult("", error=r["err"])
-    return GenResult(r["text"], r["pt"], r["ct"], 0.0, extra=_extra(r["fr"], r.get("lp")))
+    return GenResult(r["text"], r["pt"], r["ct"], 0.0, extra=_extra(r["fr"], r.get("lp"), r.get("cached", 0)))
 
 
 def _rccl_bandwidth(group, hidden: int, device, rows: int = 4096) -> float:

@@ -64,6 +64,9 @@ class GenRequest:
     # (plain lists; a banned token's -inf survives the JSON of the result all-gather as -Infinity)
     logprobs: Optional[bool] = None
     top_logprobs: Optional[int] = None
+    # added to the seed the local engine derives for the request: choice i of an ``n > 1`` chat completion
+    # (serve.py) is the same request with seed_offset i.  Hosted providers ignore it
+    seed_offset: int = 0
 
 
 def logit_bias_pairs(lb: Any) -> List[Tuple[int, float]]:

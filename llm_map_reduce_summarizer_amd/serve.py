@@ -27,8 +27,14 @@ anything else is a 400.  ``logprobs`` (a boolean) and ``top_logprobs`` (an integ
 ``top_logprobs`` most likely tokens, computed on the GPU (sampler.hip's logprobs kernels) from the logits the
 sampler sees -- after logit_bias / min_tokens and the penalties, at temperature 1, before top-k / top-p; a
 banned token's -inf is sent as -9999.0.  Anything else is a 400, as are ``logprobs`` with ``stream: true`` and
-``logprobs`` / ``top_logprobs`` on ``/v1/messages`` (that API has no such field).  Stop sequences and n > 1 are
-not supported (400).
+``logprobs`` / ``top_logprobs`` on ``/v1/messages`` (that API has no such field).  ``n`` on the chat endpoint (an
+integer in [1, 16]; not with ``stream: true``) runs the request n times with seeds ``seed + i`` and returns
+``choices[0..n-1]`` (up to ``--max-n``, default 16; ``build_app``'s own default of 1 refuses n > 1), each with its own ``finish_reason`` and ``logprobs``; ``usage.prompt_tokens`` counts the prompt
+once and ``completion_tokens`` sums the choices.  With ``--prefix-cache`` the engine keeps the full 64-token KV
+pages of every prompt findable by their token ids: a later request that begins with the same tokens (the next chat
+turn, a regenerate, a shared system prompt, the siblings of ``n``) prefills only the rest, and
+``usage.prompt_tokens_details.cached_tokens`` reports the part it did not compute.  Stop sequences are not
+supported (400), nor is ``n`` on ``/v1/messages``; prompt caching hints such as ``cache_control`` are ignored.
 
 Batching: HTTP handlers only enqueue; one engine thread owns the engine.  Single process
 (``ContinuousBatcher``): the first requests start a generate and every request that arrives while it runs
@@ -50,7 +56,7 @@ import queue
 import threading
 import time
 import uuid
-from dataclasses import asdict
+from dataclasses import asdict, replace
 from typing import Any, Dict, List, Optional, Tuple
 
 from .config import LLMConfig
@@ -83,10 +89,31 @@ def _text(content: Any) -> str:
     raise BadRequest("message content must be a string or a list of text parts")
 
 
-def _common(body: Dict[str, Any], default_temp: float) -> Tuple[int, float]:
+MAX_N = 16  # choices per chat-completions request
+
+
+def _n(body: Dict[str, Any], max_n: int = MAX_N) -> int:
+    """``n`` of a chat-completions body: the number of choices (absent or null: 1), at most ``max_n``."""
+    n = body.get("n")
+    if n is None:
+        return 1
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= MAX_N:
+        raise BadRequest("n must be an integer in [1, %d]" % MAX_N)
+    if n > max_n:
+        raise BadRequest("n > 1 is not supported" if max_n <= 1 else "n must be at most %d on this server" % max_n)
+    if n > 1 and body.get("stream"):
+        raise BadRequest("n > 1 is not available on a streamed completion: send stream: false")
+    return n
+
+
+def _common(body: Dict[str, Any], default_temp: float, max_n: Optional[int] = None) -> Tuple[int, float]:
+    """``max_n``: the most choices ``n`` may ask for on the chat endpoint (the handler expands them:
+    build_app); None: the messages endpoint, which has no ``n``."""
     if body.get("stop"):
         raise BadRequest("stop sequences are not supported")
-    if int(body.get("n", 1) or 1) != 1:
+    if max_n is not None:
+        _n(body, max_n)
+    elif int(body.get("n", 1) or 1) != 1:
         raise BadRequest("n > 1 is not supported")
     mt = body.get("max_completion_tokens", body.get("max_tokens"))
     max_tokens = int(mt) if mt is not None else 1000
@@ -190,9 +217,11 @@ def _logprob_fields(body: Dict[str, Any]) -> Dict[str, Any]:
     return out
 
 
-def openai_request(body: Dict[str, Any], default_temp: float = 1.0, vocab: Optional[int] = None) -> GenRequest:
+def openai_request(body: Dict[str, Any], default_temp: float = 1.0, vocab: Optional[int] = None,
+                   max_n: int = 1) -> GenRequest:
     """GenRequest of an OpenAI ``/v1/chat/completions`` body.  A [system?, user] chat keeps the
-    reference's request shape (same prompt rendering and seed as the in-process provider)."""
+    reference's request shape (same prompt rendering and seed as the in-process provider).  ``n`` up to
+    ``max_n`` is accepted (the caller runs the request n times, ``_n``); the default refuses n > 1."""
     msgs = body.get("messages")
     if not isinstance(msgs, list) or not msgs:
         raise BadRequest("messages must be a non-empty list")
@@ -204,7 +233,7 @@ def openai_request(body: Dict[str, Any], default_temp: float = 1.0, vocab: Optio
         if role not in ("system", "user", "assistant"):
             raise BadRequest("unsupported message role %r" % role)
         turns.append({"role": role, "content": _text(m.get("content", ""))})
-    max_tokens, temp = _common(body, default_temp)
+    max_tokens, temp = _common(body, default_temp, max_n=max_n)
     filters = {**_filters(body), **_penalties(body), **_constraints(body, max_tokens, vocab), **_logprob_fields(body)}
     roles = [t["role"] for t in turns]
     if roles in (["user"], ["system", "user"]):
@@ -260,17 +289,26 @@ def openai_logprobs(rec: Dict[str, Any], tokenizer=None) -> Dict[str, Any]:
                         for t, lp, top in zip(rec["token_ids"], rec["token_logprobs"], tops)]}
 
 
-def openai_response(res: GenResult, model: str, tokenizer=None) -> Dict[str, Any]:
-    choice: Dict[str, Any] = {"index": 0, "message": {"role": "assistant", "content": res.text},
-                              "finish_reason": _finish(res)}
-    rec = (res.extra or {}).get("logprobs")
-    if rec is not None:  # only a request that asked carries the key
-        choice["logprobs"] = openai_logprobs(rec, tokenizer)
+def openai_response(res: GenResult, model: str, tokenizer=None, siblings: Tuple[GenResult, ...] = (),
+                    cache: bool = False) -> Dict[str, Any]:
+    """``siblings``: the results of choices 1.. of an ``n > 1`` request (the prompt is counted once, the
+    completion tokens are summed).  ``cache``: the engine runs with the prefix cache, and ``usage`` reports the
+    prompt tokens it did not compute (those of choice 0)."""
+    choices = []
+    for i, r in enumerate((res,) + tuple(siblings)):
+        choice: Dict[str, Any] = {"index": i, "message": {"role": "assistant", "content": r.text},
+                                  "finish_reason": _finish(r)}
+        rec = (r.extra or {}).get("logprobs")
+        if rec is not None:  # only a request that asked carries the key
+            choice["logprobs"] = openai_logprobs(rec, tokenizer)
+        choices.append(choice)
+    completion = res.completion_tokens + sum(r.completion_tokens for r in siblings)
+    usage: Dict[str, Any] = {"prompt_tokens": res.prompt_tokens, "completion_tokens": completion,
+                             "total_tokens": res.prompt_tokens + completion}
+    if cache:
+        usage["prompt_tokens_details"] = {"cached_tokens": int((res.extra or {}).get("cached_tokens", 0))}
     return {"id": "chatcmpl-" + uuid.uuid4().hex[:24], "object": "chat.completion", "created": int(time.time()),
-            "model": model,
-            "choices": [choice],
-            "usage": {"prompt_tokens": res.prompt_tokens, "completion_tokens": res.completion_tokens,
-                      "total_tokens": res.prompt_tokens + res.completion_tokens}}
+            "model": model, "choices": choices, "usage": usage}
 
 
 def anthropic_response(res: GenResult, model: str) -> Dict[str, Any]:
@@ -477,6 +515,8 @@ class ContinuousBatcher(Batcher):
                     rec = logprobs_record(o).get("lp")
                     if rec is not None:
                         extra["logprobs"] = rec
+                    if o.cached_tokens:
+                        extra["cached_tokens"] = int(o.cached_tokens)
                     self._resolve(lp, fut, GenResult(text, o.prompt_len, len(o.token_ids), extra=extra))
 
             def feeder(done):
@@ -562,8 +602,13 @@ async def _openai_events(items, model: str):
     yield "data: [DONE]\n\n"
 
 
-def build_app(batcher: Batcher, model_name: str, api_key: Optional[str] = None, default_temp: float = 1.0):
-    """The FastAPI app (handlers enqueue on ``batcher``; ``api_key``: required Bearer / x-api-key)."""
+def build_app(batcher: Batcher, model_name: str, api_key: Optional[str] = None, default_temp: float = 1.0,
+              max_n: int = 1):
+    """The FastAPI app (handlers enqueue on ``batcher``; ``api_key``: required Bearer / x-api-key; ``max_n``:
+    the most choices a chat completion may ask for with ``n`` -- 1 refuses n > 1, the server's ``--max-n``
+    default is 16)."""
+    if not 1 <= int(max_n) <= MAX_N:
+        raise ValueError("max_n must be in [1, %d]" % MAX_N)
     from fastapi import FastAPI, Request
     from fastapi.responses import JSONResponse, PlainTextResponse, StreamingResponse
 
@@ -586,13 +631,16 @@ def build_app(batcher: Batcher, model_name: str, api_key: Optional[str] = None, 
     model_config = getattr(getattr(batcher, "provider", None), "model_config", None)
     vocab = getattr(model_config(), "vocab_size", None) if callable(model_config) else None
     tokenizer = getattr(getattr(batcher, "provider", None), "tokenizer", None)  # spells out logprobs tokens
+    cache = bool(getattr(getattr(batcher, "provider", None), "prefix_cache", False))
 
     async def _serve(request: Request, parse, render):
         if not _authorised(request):
             return _err(401, "invalid API key", "authentication_error")
         try:
             body = await request.json()
-            req = parse(body, default_temp, vocab)
+            chat = render is openai_response
+            req = parse(body, default_temp, vocab, max_n) if chat else parse(body, default_temp, vocab)
+            n = _n(body, max_n) if chat else 1
         except BadRequest as e:
             return _err(400, str(e), "invalid_request_error")
         except (ValueError, TypeError, AttributeError) as e:
@@ -600,10 +648,15 @@ def build_app(batcher: Batcher, model_name: str, api_key: Optional[str] = None, 
         model = body.get("model") or model_name
         if body.get("stream") and render is openai_response:
             return StreamingResponse(_openai_events(batcher.stream(req), model), media_type="text/event-stream")
-        res = await batcher.submit(req)
-        if res.error:
-            return _err(500, res.error, "engine_error")
-        out = render(res, model, tokenizer) if render is openai_response else render(res, model)
+        # n > 1 (chat endpoint): n engine requests with seeds seed + i, enqueued together (with the prefix cache
+        # the siblings share the prompt's full pages and prefill its tail only)
+        res, *more = await asyncio.gather(*[batcher.submit(replace(req, seed_offset=i) if i else req)
+                                            for i in range(n)])
+        for r in (res, *more):
+            if r.error:
+                return _err(500, r.error, "engine_error")
+        out = (render(res, model, tokenizer, tuple(more), cache) if render is openai_response
+               else render(res, model))
         if body.get("stream"):  # Anthropic: the whole message as one event
             async def events():
                 yield "data: %s\n\n" % json.dumps(out)
@@ -631,7 +684,11 @@ def build_app(batcher: Batcher, model_name: str, api_key: Optional[str] = None, 
     @app.get("/metrics")
     async def metrics():
         lines = []
-        for k, v in batcher.stats.items():
+        stats = dict(batcher.stats)
+        prefix_stats = getattr(getattr(batcher, "provider", None), "prefix_stats", None)
+        if callable(prefix_stats):  # prefix_hit_tokens / prefix_hit_requests / prefix_evictions, cache on only
+            stats.update(prefix_stats())
+        for k, v in stats.items():
             kind = "gauge" if k == "max_batch_seen" else "counter"
             lines += ["# TYPE mrsum_%s %s" % (k, kind), "mrsum_%s %s" % (k, v)]
         return PlainTextResponse("\n".join(lines) + "\n", media_type="text/plain; version=0.0.4")
@@ -655,6 +712,11 @@ def main(argv: Optional[List[str]] = None) -> int:
     ap.add_argument("--batch-window-ms", type=float, default=5.0)
     ap.add_argument("--api-key", default=os.environ.get("MRSUM_SERVE_API_KEY"))
     ap.add_argument("--no-graphs", action="store_true")
+    ap.add_argument("--prefix-cache", action="store_const", const=True, default=None,
+                    help="share the KV pages of prompts that begin with the same tokens ($ENGINE_PREFIX_CACHE=1; "
+                         "TP=1 engines)")
+    ap.add_argument("--max-n", type=int, default=MAX_N, choices=range(1, MAX_N + 1), metavar="[1-16]",
+                    help="most choices a chat completion may ask for with n (1: refuse n > 1)")
     ap.add_argument("--log-level", default="INFO")
     a = ap.parse_args(argv)
     logging.basicConfig(level=getattr(logging, a.log_level.upper()), format="%(asctime)s %(name)s %(message)s")
@@ -669,7 +731,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     if torch.cuda.is_available():
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
     provider = LocalEngineProvider(a.model, LLMConfig(), tp=a.tp, dtype=a.dtype, weights=a.weights,
-                                   max_model_len=a.max_model_len, use_graphs=not a.no_graphs, parallel=a.parallel)
+                                   max_model_len=a.max_model_len, use_graphs=not a.no_graphs, parallel=a.parallel,
+                                   prefix_cache=a.prefix_cache)
     provider.warm()
     batcher = make_batcher(provider, a.max_batch, a.batch_window_ms / 1000.0)
     if pdist.is_initialized() and provider.par.rank != 0:
@@ -678,7 +741,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         return 0
     import uvicorn
     batcher.start()
-    app = build_app(batcher, a.served_model_name or a.model, a.api_key)
+    app = build_app(batcher, a.served_model_name or a.model, a.api_key, max_n=a.max_n)
     try:
         uvicorn.run(app, host=a.host, port=a.port, log_level=a.log_level.lower())
     finally:
