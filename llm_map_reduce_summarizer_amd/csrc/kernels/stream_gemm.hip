@@ -766,8 +766,28 @@ MRSUM_API int mrsum_stream_fp8(const void* x, int ldx, const void* W, const floa
 //   [3072, 3584) 2-bit plane: 8 l + 4 h = one dword per half; with q = 2 (i & 1) + (e >> 2), b = e & 3:
 //                code bit 4 at bit 8 b + 4 - q, sign at bit 8 b + 7 - {0, 1, 2, 7}[q]      (1 ds_read_b64)
 // so that decode is whole-dword mask / shift / add and four v_perm_b32 per MFMA step.
+//
+// p13: one more bit off.  hi is kept as the 5-bit code sign << 4 | c4: c4 = 0 for e7 = 0, else c4 = e7 - base7 + 1
+// in 1..15, base7 = max(max e7 of the matrix - 14, 1) -- a window of 15 e7 values = 30 binades, which the
+// project's own initialisation leaves by one or two elements in 10^8.  Those EXCEPTIONS (e7 != 0, e7 < base7)
+// are stored with c4 = 0, sign and lo verbatim, and listed with their true e7 as the words
+//   kb << 18 | lane << 12 | (8 i + e) << 7 | e7        (kb = k block of the matrix, lane / i / e as above)
+// sorted by (16-row group, word), with offsets exoff[G] .. exoff[G + 1] per group.  A matrix is p13-packable
+// iff no group holds more than P13_EXCAP exceptions.  The wave that owns group G reads its count once ahead of
+// the ring (scalar loads: they do not count against the ring's vmcnt), keeps a non-empty group's words in
+// registers, compares one k-block number per iteration and ORs the e7 into the hi byte of the one lane's
+// fragment on a match; a split-K workgroup only ever matches the k blocks of its own range.
+// Tile = 3328 bytes: 3 x 16 B/lane + 1 x 4 B/lane DMA instructions per wave per slot (the bf16 kernel's four):
+//   [   0, 2048) lo plane and [2048, 3072) 4-bit plane: as p14 (the 4-bit plane holds c4)
+//   [3072, 3328) sign plane: 4 l = one dword per lane; with q = 2 i + (e >> 2), b = e & 3: sign at bit 8 b + q,
+//                so the four signs of a half step are (dword << (7 - q)) & 0x80808080.
 namespace {
-constexpr int P14_TILE = 3584, P14_NIB = 2048, P14_TWO = 3072;
+constexpr int P13_EXCAP = 8;  // exceptions per 16-row group (ops/reference.py P13_EXCAP)
+template <int BITS> struct Packed;
+template <> struct Packed<14> { enum { TILE = 3584, NIB = 2048, TOP = 3072, NW = 5, WINDOW = 31 }; };
+template <> struct Packed<13> { enum { TILE = 3328, NIB = 2048, TOP = 3072, NW = 4, WINDOW = 15 }; };
+constexpr int P14_TILE = Packed<14>::TILE, P14_NIB = Packed<14>::NIB, P14_TWO = Packed<14>::TOP;
+constexpr int P13_TILE = Packed<13>::TILE, P13_NIB = Packed<13>::NIB, P13_SGN = Packed<13>::TOP;
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 template <int AUX = 0>
@@ -787,31 +807,57 @@ __device__ __forceinline__ uint32_t p14_hi4(uint32_t q4, uint32_t s2, uint32_t b
 }
 
 // A fragment of MFMA step i: l0 / l1 = lo bytes of e = 0..3 / 4..7, nb = the step's 4-bit dword
+// the interleave of both widths: hi bytes h0 / h1 over lo bytes l0 / l1 = the step's 8 bf16
+__device__ __forceinline__ u32x4 packed_weave(uint32_t h0, uint32_t h1, uint32_t l0, uint32_t l1) {
+    return u32x4{__builtin_amdgcn_perm(h0, l0, 0x05010400u), __builtin_amdgcn_perm(h0, l0, 0x07030602u),
+                 __builtin_amdgcn_perm(h1, l1, 0x05010400u), __builtin_amdgcn_perm(h1, l1, 0x07030602u)};
+}
+
 template <int PAR>
-__device__ __forceinline__ bf16x8 p14_frag(uint32_t l0, uint32_t l1, uint32_t nb, uint32_t s2, uint32_t base4) {
+__device__ __forceinline__ u32x4 p14_frag(uint32_t l0, uint32_t l1, uint32_t nb, uint32_t s2, uint32_t base4) {
     const uint32_t h0 = p14_hi4<2 * PAR>(nb & 0x0f0f0f0fu, s2, base4);
     const uint32_t h1 = p14_hi4<2 * PAR + 1>((nb >> 4) & 0x0f0f0f0fu, s2, base4);
-    const u32x4 o = {__builtin_amdgcn_perm(h0, l0, 0x05010400u), __builtin_amdgcn_perm(h0, l0, 0x07030602u),
-                     __builtin_amdgcn_perm(h1, l1, 0x05010400u), __builtin_amdgcn_perm(h1, l1, 0x07030602u)};
-    return __builtin_bit_cast(bf16x8, o);
+    return packed_weave(h0, h1, l0, l1);
+}
+
+// p13: hi bytes of 4 weights from their 4-bit codes one per byte and the lane's sign dword, Q = 2 i + (e >> 2)
+template <int Q>
+__device__ __forceinline__ uint32_t p13_hi4(uint32_t q4, uint32_t sg, uint32_t base4) {
+    const uint32_t nz = (q4 + 0x0f0f0f0fu) & 0x10101010u;  // bit 4 of a byte: its code is not 0
+    const uint32_t on = (nz << 4) - (nz >> 4);              // 0xff in those bytes
+    return (q4 + (on & base4)) | ((sg << (7 - Q)) & 0x80808080u);
+}
+
+template <int I>
+__device__ __forceinline__ u32x4 p13_frag(uint32_t l0, uint32_t l1, uint32_t nb, uint32_t sg, uint32_t base4) {
+    const uint32_t h0 = p13_hi4<2 * I>(nb & 0x0f0f0f0fu, sg, base4);
+    const uint32_t h1 = p13_hi4<2 * I + 1>((nb >> 4) & 0x0f0f0f0fu, sg, base4);
+    return packed_weave(h0, h1, l0, l1);
 }
 }  // namespace
 
-template <int MT, int EPI, int WPB>
-__global__ __launch_bounds__(64 * WPB, 1) void stream_p14_kernel(const bf16* __restrict__ x, int ldx,
-                                                                 const unsigned char* __restrict__ W, int base7,
-                                                                 int K, int M, void* __restrict__ out, int ldo,
-                                                                 int kper, float* __restrict__ parts,
-                                                                 int* __restrict__ counters, const NormArgs e) {
+// One kernel for both packed widths (BITS = 14 | 13): tile size, DMA issue list, NI and the fragment decode
+// come from the format; exoff / exlist (p13 only) are the matrix's exception list.
+template <int BITS, int MT, int EPI, int WPB>
+__global__ __launch_bounds__(64 * WPB, 1) void stream_packed_kernel(const bf16* __restrict__ x, int ldx,
+                                                                    const unsigned char* __restrict__ W, int base7,
+                                                                    const int* __restrict__ exoff,
+                                                                    const uint32_t* __restrict__ exlist,
+                                                                    int K, int M, void* __restrict__ out, int ldo,
+                                                                    int kper, float* __restrict__ parts,
+                                                                    int* __restrict__ counters, const NormArgs e) {
+    using F = Packed<BITS>;
+    constexpr int TILE = F::TILE;
     constexpr int R = 16 * WPB, BM = 16 * MT;
-    constexpr int WBYTES = WPB * P14_TILE, SLOT = WBYTES + BM * 256;
-    // the slot is 12.5 % smaller than the bf16 one: a deeper ring keeps the weight bytes in flight (cap 8, as
-    // the fp8 one-row variant)
+    constexpr int WBYTES = WPB * TILE, SLOT = WBYTES + BM * 256;
+    // the slot is 12.5 % (p13: 19 %) smaller than the bf16 one: a deeper ring keeps the weight bytes in flight
+    // (cap 8, as the fp8 one-row variant)
     constexpr int D = (LDS_BUDGET / SLOT) < 8 ? (LDS_BUDGET / SLOT) : 8;
     static_assert(D >= 2, "ring too shallow");
     constexpr int XP = 2 * BM / 8;
     constexpr int XI = (XP + WPB - 1) / WPB;
-    constexpr int NI = 5 + XI;                   // DMA instructions per wave per slot (W: 3 x 1 KiB + 2 x 256 B)
+    // DMA instructions per wave per slot (W: 3 x 1 KiB + 2 x 256 B | 3 x 1 KiB + 1 x 256 B)
+    constexpr int NI = F::NW + XI;
     static_assert(NI * (D - 2) < 64, "vmcnt range");
     __shared__ __attribute__((aligned(1024))) char lds[D * SLOT + LDS_XTRA];
     float* const s_ss = reinterpret_cast<float*>(lds + D * SLOT + 1024);
@@ -821,8 +867,17 @@ __global__ __launch_bounds__(64 * WPB, 1) void stream_p14_kernel(const bf16* __r
     const int ks = blockIdx.y * kper;
     const int nkb = kper / KBLK;
 
+    // p13: this wave's exception range, read with scalar loads issued ahead of the ring (first used after the
+    // prologue; nothing of it counts against vmcnt)
+    int ex0 = 0, nex = 0;
+    if constexpr (BITS == 13) {
+        const int G = n0 / 16 + __builtin_amdgcn_readfirstlane(w);
+        ex0 = exoff[G];
+        nex = exoff[G + 1] - ex0;
+    }
+
     // this wave's tiles: group n0 / 16 + w, k blocks ks / 128 ...
-    const unsigned char* const wsrc = W + ((size_t)(n0 / 16 + w) * (K / KBLK) + ks / KBLK) * P14_TILE;
+    const unsigned char* const wsrc = W + ((size_t)(n0 / 16 + w) * (K / KBLK) + ks / KBLK) * TILE;
     const int prow = lane >> 3, pslot = lane & 7;
     const bf16* xsrc[XI];
     int xdst[XI];
@@ -834,16 +889,16 @@ __global__ __launch_bounds__(64 * WPB, 1) void stream_p14_kernel(const bf16* __r
         xsrc[i] = x + (size_t)min(row, M - 1) * ldx + ks + 8 * (8 * (qq & 1) + (pslot ^ prow));
         xdst[i] = q < XP ? WBYTES + q * 1024 : -1;
     }
-#define ISSUE14(slot, kb)                                                                            \
+#define ISSUEP(slot, kb)                                                                             \
     {                                                                                                \
         char* base = lds + (slot) * SLOT;                                                            \
-        char* wb = base + w * P14_TILE;                                                              \
-        const unsigned char* ws = wsrc + (size_t)(kb) * P14_TILE;                                    \
+        char* wb = base + w * TILE;                                                                  \
+        const unsigned char* ws = wsrc + (size_t)(kb) * TILE;                                        \
         glds16<2>(ws + 16 * lane, wb);                                                               \
         glds16<2>(ws + 1024 + 16 * lane, wb + 1024);                                                 \
-        glds16<2>(ws + P14_NIB + 16 * lane, wb + P14_NIB);                                           \
-        glds4<2>(ws + P14_TWO + 4 * lane, wb + P14_TWO);                                             \
-        glds4<2>(ws + P14_TWO + 256 + 4 * lane, wb + P14_TWO + 256);                                 \
+        glds16<2>(ws + F::NIB + 16 * lane, wb + F::NIB);                                             \
+        glds4<2>(ws + F::TOP + 4 * lane, wb + F::TOP);                                               \
+        if constexpr (BITS == 14) glds4<2>(ws + F::TOP + 256 + 4 * lane, wb + F::TOP + 256);         \
         _Pragma("unroll") for (int i = 0; i < XI; ++i)                                               \
             glds16(xsrc[i] + (kb) * KBLK, xdst[i] >= 0 ? base + xdst[i] : lds + D * SLOT);           \
     }
@@ -853,7 +908,24 @@ __global__ __launch_bounds__(64 * WPB, 1) void stream_p14_kernel(const bf16* __r
     for (int m = 0; m < MT; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
 
 #pragma unroll
-    for (int s = 0; s < D - 1; ++s) ISSUE14(s, min(s, nkb - 1));
+    for (int s = 0; s < D - 1; ++s) ISSUEP(s, min(s, nkb - 1));
+
+    // p13: a non-empty group's exception words in registers (unused slots: a k block no matrix has), and the
+    // next k block of this workgroup's range that holds one
+    const uint32_t kb0 = (uint32_t)(ks / KBLK);
+    uint32_t ex[P13_EXCAP], exkb = ~0u;
+    if constexpr (BITS == 13) {
+#pragma unroll
+        for (int c = 0; c < P13_EXCAP; ++c) ex[c] = ~0u;
+        if (nex > 0) {
+#pragma unroll
+            for (int c = 0; c < P13_EXCAP; ++c) {
+                if (c < nex) ex[c] = __builtin_amdgcn_readfirstlane(exlist[ex0 + c]);
+                const uint32_t kbc = ex[c] >> 18;
+                if (kbc >= kb0) exkb = min(exkb, kbc);
+            }
+        }
+    }
 
     const uint32_t base4 = (uint32_t)(base7 - 1) * 0x01010101u;  // added to every non-zero code
     const int r = lane & 15, g = lane >> 4;
@@ -861,42 +933,74 @@ __global__ __launch_bounds__(64 * WPB, 1) void stream_p14_kernel(const bf16* __r
         if (j + D - 2 < nkb) wait_vmcnt<NI * (D - 2)>();
         else wait_vmcnt<0>();
         raw_barrier();
-        if (j + D - 1 < nkb) ISSUE14((j + D - 1) % D, j + D - 1);
-        const char* wl = lds + (j % D) * SLOT + w * P14_TILE;
+        if (j + D - 1 < nkb) ISSUEP((j + D - 1) % D, j + D - 1);
+        const char* wl = lds + (j % D) * SLOT + w * TILE;
         const char* xl = lds + (j % D) * SLOT + WBYTES;
         const u32x4 lo0 = *reinterpret_cast<const u32x4*>(wl + 16 * lane);
         const u32x4 lo1 = *reinterpret_cast<const u32x4*>(wl + 1024 + 16 * lane);
-        const u32x4 nb = *reinterpret_cast<const u32x4*>(wl + P14_NIB + 16 * lane);
-        const u32x2 s2 = *reinterpret_cast<const u32x2*>(wl + P14_TWO + 8 * lane);
-        bf16x8 av[4];
-        av[0] = p14_frag<0>(lo0[0], lo0[1], nb[0], s2.x, base4);
-        av[1] = p14_frag<1>(lo0[2], lo0[3], nb[1], s2.x, base4);
-        av[2] = p14_frag<0>(lo1[0], lo1[1], nb[2], s2.y, base4);
-        av[3] = p14_frag<1>(lo1[2], lo1[3], nb[3], s2.y, base4);
+        const u32x4 nb = *reinterpret_cast<const u32x4*>(wl + F::NIB + 16 * lane);
+        u32x4 av[4];
+        if constexpr (BITS == 14) {
+            const u32x2 s2 = *reinterpret_cast<const u32x2*>(wl + F::TOP + 8 * lane);
+            av[0] = p14_frag<0>(lo0[0], lo0[1], nb[0], s2.x, base4);
+            av[1] = p14_frag<1>(lo0[2], lo0[3], nb[1], s2.x, base4);
+            av[2] = p14_frag<0>(lo1[0], lo1[1], nb[2], s2.y, base4);
+            av[3] = p14_frag<1>(lo1[2], lo1[3], nb[3], s2.y, base4);
+        } else {
+            const uint32_t sg = *reinterpret_cast<const uint32_t*>(wl + F::TOP + 4 * lane);
+            av[0] = p13_frag<0>(lo0[0], lo0[1], nb[0], sg, base4);
+            av[1] = p13_frag<1>(lo0[2], lo0[3], nb[1], sg, base4);
+            av[2] = p13_frag<2>(lo1[0], lo1[1], nb[2], sg, base4);
+            av[3] = p13_frag<3>(lo1[2], lo1[3], nb[3], sg, base4);
+            if (kb0 + (uint32_t)j == exkb) {  // wave-uniform, rare: restore this k block's exceptions
+                const uint32_t cur = exkb;
+                exkb = ~0u;
+#pragma unroll
+                for (int c = 0; c < P13_EXCAP; ++c) {
+                    uint32_t xc = ex[c];
+                    // opaque: the word is decoded here, in the cold block (the loop-invariant lane / dword
+                    // predicates of all eight words were hoisted into every wave's prologue otherwise)
+                    asm volatile("" : "+s"(xc));
+                    const uint32_t kbc = xc >> 18;
+                    if (kbc == cur) {
+                        const int sl = (xc >> 7) & 31;  // 8 i + e: dword (e >> 1) of step i, half e & 1
+                        const uint32_t v = lane == (int)((xc >> 12) & 63) ? (xc & 127u) << (8 + 16 * (sl & 1)) : 0u;
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+#pragma unroll
+                            for (int d = 0; d < 4; ++d) av[i][d] |= sl >> 1 == 4 * i + d ? v : 0u;
+                    } else if (kbc > cur) {
+                        exkb = min(exkb, kbc);
+                    }
+                }
+            }
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
                 const u32x4 bv = *reinterpret_cast<const u32x4*>(xl + img_off(16 * m + r, 4 * i + g));
-                acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[i], __builtin_bit_cast(bf16x8, bv), acc[m], 0, 0, 0);
+                acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, av[i]),
+                                                                 __builtin_bit_cast(bf16x8, bv), acc[m], 0, 0, 0);
             }
         }
     }
-#undef ISSUE14
+#undef ISSUEP
 
     stream_epilogue<MT, EPI, WPB>(acc, lds, s_ss, n0, M, out, ldo, parts, counters, e);
 }
 
-// Same contract as mrsum_stream_gemm at M <= 64 and without a TP push (``ar`` must be null), with W the p14
-// tiles of a packable [N, K] bf16 matrix (mrsum_p14_pack) and base7 its window base.  Bit-identical to
-// mrsum_stream_gemm on the unpacked matrix with the same (M, splits, wpb).
-MRSUM_API int mrsum_stream_p14(const void* x, int ldx, const void* W, int base7, int N, int K, int M, void* out,
-                               int ldo, int epi, int splits, int wpb, void* parts, int* counters, const float* ssq,
-                               int ssq_tiles, float eps, void* resid, int ldr, float* ssp, void* ar, hipStream_t s) {
+// Checks and dispatch of both packed widths (exoff / exlist: p13 only).
+template <int BITS>
+static int launch_packed(const void* x, int ldx, const void* W, int base7, const int* exoff, const uint32_t* exlist,
+                         int N, int K, int M, void* out, int ldo, int epi, int splits, int wpb, void* parts,
+                         int* counters, const float* ssq, int ssq_tiles, float eps, void* resid, int ldr, float* ssp,
+                         void* ar, hipStream_t s) {
     if (M <= 0) return 0;
     if (wpb < 4 || wpb > 8 || M > 64 || K % KBLK || N % (16 * wpb) || splits < 1 || (K / KBLK) % splits ||
-        epi < EPI_BF16 || epi > EPI_RESID_SPLIT || base7 < 1 || base7 > 97 || ar)
+        epi < EPI_BF16 || epi > EPI_RESID_SPLIT || base7 < 1 || base7 > 128 - Packed<BITS>::WINDOW || ar)
         return (int)hipErrorInvalidValue;
+    if (BITS == 13 && (!exoff || !exlist || K / KBLK >= 0x3fff)) return (int)hipErrorInvalidValue;
     const bool split_epi = epi == EPI_SWIGLU_SPLIT || epi == EPI_RESID_SPLIT;
     if (epi != EPI_F32_PARTIAL && !split_epi && splits != 1) return (int)hipErrorInvalidValue;
     if (split_epi && (!parts || !counters)) return (int)hipErrorInvalidValue;
@@ -912,8 +1016,9 @@ MRSUM_API int mrsum_stream_p14(const void* x, int ldx, const void* W, int base7,
     auto X = (const bf16*)x;
     auto Wp = (const unsigned char*)W;
     auto P = (float*)parts;
-#define L14(MT_, EPI_, WPB_) \
-    stream_p14_kernel<MT_, EPI_, WPB_><<<grid, block, 0, s>>>(X, ldx, Wp, base7, K, M, out, ldo, kper, P, counters, e)
+#define L14(MT_, EPI_, WPB_)                                                                                      \
+    stream_packed_kernel<BITS, MT_, EPI_, WPB_><<<grid, block, 0, s>>>(X, ldx, Wp, base7, exoff, exlist, K, M, out, \
+                                                                       ldo, kper, P, counters, e)
 #define BY_WPB14(MT_, EPI_)                         \
     switch (wpb) {                                  \
         case 4: L14(MT_, EPI_, 4); break;           \
@@ -938,6 +1043,26 @@ MRSUM_API int mrsum_stream_p14(const void* x, int ldx, const void* W, int base7,
 #undef BY_WPB14
 #undef L14
     return (int)hipGetLastError();
+}
+
+// Same contract as mrsum_stream_gemm at M <= 64 and without a TP push (``ar`` must be null), with W the p14
+// tiles of a packable [N, K] bf16 matrix (mrsum_p14_pack) and base7 its window base.  Bit-identical to
+// mrsum_stream_gemm on the unpacked matrix with the same (M, splits, wpb).
+MRSUM_API int mrsum_stream_p14(const void* x, int ldx, const void* W, int base7, int N, int K, int M, void* out,
+                               int ldo, int epi, int splits, int wpb, void* parts, int* counters, const float* ssq,
+                               int ssq_tiles, float eps, void* resid, int ldr, float* ssp, void* ar, hipStream_t s) {
+    return launch_packed<14>(x, ldx, W, base7, nullptr, nullptr, N, K, M, out, ldo, epi, splits, wpb, parts, counters,
+                             ssq, ssq_tiles, eps, resid, ldr, ssp, ar, s);
+}
+
+// The p13 form of the same contract: W the p13 tiles of a p13-packable matrix (mrsum_p13_pack), exoff int
+// [N / 16 + 1] and exlist (at least one readable word) its exception list.
+MRSUM_API int mrsum_stream_p13(const void* x, int ldx, const void* W, int base7, const int* exoff,
+                               const unsigned int* exlist, int N, int K, int M, void* out, int ldo, int epi, int splits,
+                               int wpb, void* parts, int* counters, const float* ssq, int ssq_tiles, float eps,
+                               void* resid, int ldr, float* ssp, void* ar, hipStream_t s) {
+    return launch_packed<13>(x, ldx, W, base7, exoff, exlist, N, K, M, out, ldo, epi, splits, wpb, parts, counters,
+                             ssq, ssq_tiles, eps, resid, ldr, ssp, ar, s);
 }
 
 // p14 packer: one pass for the matrix's largest e7, one that writes the tiles and counts the elements
@@ -1004,5 +1129,73 @@ MRSUM_API int mrsum_p14_pack(const void* W, int N, int K, void* packed, int* sta
     p14_max_kernel<<<blocks, 256, 0, s>>>((const uint4*)W, n16, stats);
     p14_pack_kernel<<<(unsigned)((size_t)(N / 16) * (K / KBLK)), 64, 0, s>>>((const bf16*)W, K, (unsigned char*)packed,
                                                                               stats);
+    return (int)hipGetLastError();
+}
+
+// p13 packer: the same two passes.  The second appends every exception word to its group's bucket (excnt[G]
+// counts all of them, exbuf[G][P13_EXCAP] keeps the first P13_EXCAP to arrive: a group above the cap makes the
+// matrix unpackable whatever its bucket holds); the caller sorts each bucket, which makes the list's order
+// independent of the arrival order.
+namespace {
+__global__ __launch_bounds__(64) void p13_pack_kernel(const bf16* __restrict__ W, int K, unsigned char* __restrict__ P,
+                                                      int* __restrict__ stats, int* __restrict__ excnt,
+                                                      uint32_t* __restrict__ exbuf) {
+    const int lane = threadIdx.x, r = lane & 15, g = lane >> 4;
+    const int nkb = K / KBLK;
+    const size_t tile = blockIdx.x;
+    const int G = (int)(tile / nkb), kb = (int)(tile % nkb);
+    const int base7 = max(stats[0] - 14, 1);
+    const uint4* src = reinterpret_cast<const uint4*>(W + (size_t)(16 * G + r) * K + (size_t)kb * KBLK + 8 * g);
+    uint32_t lo[8], nb[4], sg = 0u;
+    int nexc = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint4 v = src[4 * i];
+        const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+        lo[2 * i] = lo[2 * i + 1] = nb[i] = 0u;
+#pragma unroll
+        for (int el = 0; el < 8; ++el) {
+            const uint32_t wv = (d[el >> 1] >> (16 * (el & 1))) & 0xffffu;
+            const int e7 = (wv >> 8) & 0x7f;
+            const bool exc = e7 != 0 && e7 < base7;
+            const uint32_t c4 = e7 == 0 || exc ? 0u : (uint32_t)(e7 - base7 + 1);  // <= 15: base7 >= max e7 - 14
+            if (exc) {
+                ++nexc;
+                const int at = atomicAdd(excnt + G, 1);
+                if (at < P13_EXCAP)
+                    exbuf[(size_t)G * P13_EXCAP + at] = (uint32_t)kb << 18 | (uint32_t)lane << 12 |
+                                                        (uint32_t)(8 * i + el) << 7 | (uint32_t)e7;
+            }
+            const int b = el & 3;
+            lo[2 * i + (el >> 2)] |= (wv & 0xffu) << (8 * b);
+            nb[i] |= c4 << (8 * b + 4 * (el >> 2));
+            sg |= (wv >> 15) << (8 * b + 2 * i + (el >> 2));
+        }
+    }
+    unsigned char* t = P + tile * P13_TILE;
+    *reinterpret_cast<uint4*>(t + 16 * lane) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+    *reinterpret_cast<uint4*>(t + 1024 + 16 * lane) = make_uint4(lo[4], lo[5], lo[6], lo[7]);
+    *reinterpret_cast<uint4*>(t + P13_NIB + 16 * lane) = make_uint4(nb[0], nb[1], nb[2], nb[3]);
+    *reinterpret_cast<uint32_t*>(t + P13_SGN + 4 * lane) = sg;
+    if (nexc) atomicAdd(stats + 1, nexc);
+}
+}  // namespace
+
+// W bf16 [N, K] contiguous (N % 16 == 0, K % 128 == 0, K / 128 < 16383) -> packed N * K * 13 / 8 bytes; stats
+// int[2] = {largest e7, exceptions} (base7 = max(stats[0] - 14, 1)); excnt int [N / 16] = exceptions per 16-row
+// group; exbuf uint32 [N / 16][P13_EXCAP] = each group's first exception words, unsorted.  Packable iff no
+// excnt exceeds P13_EXCAP.
+MRSUM_API int mrsum_p13_pack(const void* W, int N, int K, void* packed, int* stats, int* excnt, unsigned int* exbuf,
+                             hipStream_t s) {
+    if (N <= 0 || K <= 0 || N % 16 || K % KBLK || K / KBLK >= 0x3fff || !W || !packed || !stats || !excnt || !exbuf)
+        return (int)hipErrorInvalidValue;
+    hipError_t rc = hipMemsetAsync(stats, 0, 2 * sizeof(int), s);
+    if (rc == hipSuccess) rc = hipMemsetAsync(excnt, 0, (size_t)(N / 16) * sizeof(int), s);
+    if (rc != hipSuccess) return (int)rc;
+    const size_t n16 = (size_t)N * K / 8;
+    const int blocks = (int)((n16 + 255) / 256 < 4096 ? (n16 + 255) / 256 : 4096);
+    p14_max_kernel<<<blocks, 256, 0, s>>>((const uint4*)W, n16, stats);
+    p13_pack_kernel<<<(unsigned)((size_t)(N / 16) * (K / KBLK)), 64, 0, s>>>((const bf16*)W, K, (unsigned char*)packed,
+                                                                              stats, excnt, exbuf);
     return (int)hipGetLastError();
 }

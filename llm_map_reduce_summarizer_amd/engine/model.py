@@ -34,6 +34,7 @@ from __future__ import annotations
 import hashlib
 import math
 import os
+import sys
 from dataclasses import dataclass
 from typing import Callable, List, Optional
 
@@ -246,7 +247,11 @@ class LlamaModel:
         """bf16 TP=1 models on the GPU with MRSUM_P14=1: the decode weights (norm gains folded in, as the
         decode kernels read them) get a lossless 14-bit packed copy (ops.hip.p14_attach) that the stream
         GEMM reads instead -- 12.5 % fewer weight bytes per decode step.  The bf16 tensors stay: prefill and
-        the other decode kernels read them, and they are the fallback of an unpackable matrix."""
+        the other decode kernels read them, and they are the fallback of an unpackable matrix.
+
+        Each weight holds ONE packed form (``self.p14`` lists them all): the 13-bit form with an exception list
+        (ops.hip.p13_attach, 18.75 % fewer bytes) where its role reads it and the matrix is p13-packable
+        (MRSUM_P13=0: never), else p14 where packable, else none."""
         self.p14 = []
         if self.weight_dtype != "bf16" or self.tp_size != 1 or self.device.type != "cuda" \
                 or self.dtype != torch.bfloat16:
@@ -257,14 +262,25 @@ class LlamaModel:
         todo = [(self.lm_head, "lm_head")]
         for lw in self.layers:
             todo += [(lw.wqkv, "qkv"), (lw.wo, "o"), (lw.wgu, "gate_up"), (lw.wdown, "down")]
+        n13 = n14 = n16 = nex = 0
         for w, role in todo:
-            if hip.p14_role_used(role) and w.shape[0] % 16 == 0 and w.shape[1] % 128 == 0:
-                self.p14.append(hip.p14_attach(w, role))
+            if w.shape[0] % 16 or w.shape[1] % 128:
+                continue
+            pw = hip.packed_attach(w, role)
+            if pw is None:
+                continue
+            self.p14.append(pw)
+            if isinstance(pw, hip.Packed13Weight):
+                n13, nex = n13 + 1, nex + pw.nex
+            else:
+                n14, n16 = n14 + pw.packable, n16 + (not pw.packable)
+        print("packed decode weights: %d p13 (%d exceptions), %d p14, %d left bf16" % (n13, nex, n14, n16),
+              file=sys.stderr)
 
     def __del__(self):
         try:  # the registry keeps the packed copies (and the weights) alive: drop them with the model
             for pw in getattr(self, "p14", ()):
-                _hip().p14_detach(pw.w)
+                _hip().packed_detach(pw.w)
         except Exception:  # noqa: BLE001 -- interpreter shutdown
             pass
 

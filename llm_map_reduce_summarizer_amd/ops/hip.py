@@ -50,6 +50,9 @@ _SIGS = {
     "mrsum_stream_p14": [_vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp,
                          _vp, _vp, _c_int, _c_float, _vp, _c_int, _vp, _vp, _vp],
     "mrsum_p14_pack": [_vp, _c_int, _c_int, _vp, _vp, _vp],
+    "mrsum_stream_p13": [_vp, _c_int, _vp, _c_int, _vp, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int,
+                         _c_int, _vp, _vp, _vp, _c_int, _c_float, _vp, _c_int, _vp, _vp, _vp],
+    "mrsum_p13_pack": [_vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp],
     "mrsum_skinny_fp8": [_vp, _c_int, _vp, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp,
                          _c_int, _c_float, _vp, _c_int, _vp, _vp, _c_int, _vp],
     "mrsum_skinny_fp8_resid_capacity": [],
@@ -1097,8 +1100,17 @@ def _stream_launch(x, w, out, epi, splits, ldo, wpb, parts, counters, norm, resi
         _req(ssp.shape[1] == N // (16 * wpb), "stream_gemm: ssp tiles")
     sq, tiles, eps = _norm_args(x, norm)
     rp, ldr, sp = _resid_args(x, N, epi, resid, ssp)
+    packed_ok = M <= SKINNY_MAX_M and not slab_m and ar is None
+    p3 = p13_lookup(w) if _P13 else None
+    if p3 is not None and packed_ok and p13_takes(p3.role, M):
+        STATS["stream_p14"] += 1  # launches of the packed kernel, either width
+        STATS["stream_p13"] += 1
+        _check(_fn("mrsum_stream_p13")(_p(x), x.stride(0), _p(p3.packed), p3.base7, _p(p3.exoff), _p(p3.exlist), N, K,
+                                       M, _p(out), ldo, epi, splits, wpb, _p(parts), _p(counters), sq, tiles, eps, rp,
+                                       ldr, sp, None, _stream()), "stream_p13")
+        return out
     pw = p14_lookup(w) if _P14 else None
-    if pw is not None and M <= SKINNY_MAX_M and not slab_m and ar is None and p14_takes(pw.role, M):
+    if pw is not None and packed_ok and p14_takes(pw.role, M):
         STATS["stream_p14"] += 1
         _check(_fn("mrsum_stream_p14")(_p(x), x.stride(0), _p(pw.packed), pw.base7, N, K, M, _p(out), ldo, epi, splits,
                                        wpb, _p(parts), _p(counters), sq, tiles, eps, rp, ldr, sp, None, _stream()),
@@ -1191,6 +1203,115 @@ def p14_detach(w: torch.Tensor) -> None:
 
 def p14_lookup(w: torch.Tensor) -> Optional[PackedWeight]:
     return _P14.get((w.data_ptr(), w.shape[0], w.shape[1]))
+
+
+# ------------------------------------------------------------------ p13: 13-bit packed bf16 with an exception list
+# (stream_gemm.hip "p13"; ops/reference.py p13_pack_ref is the bit-level reference, exception list included).
+# A weight holds ONE packed form: p13 where its role is in this plan and the matrix is p13-packable, else p14 by
+# _P14_PLAN, else none.  MRSUM_P13=0 keeps p14 only (A/B runs in one tree); MRSUM_P14=0 turns both off.
+# (role, row bucket) pairs whose stream GEMM reads the p13 form, adopted where the kernel ran faster inside whole
+# headline steps (docs/decode_latency.md "p13", profiles/p13_e2e_10h_kernel_summary.txt, us per dispatch p14 plan
+# -> p13): gate_up 35.8 -> 33.0 at up to 16 rows, LM head 164.5 -> 157.0 and down 22.9 -> 22.1 at up to 16 rows.
+# gate_up at 39 rows came out level (36.5 -> 36.9: the 48-row slot keeps a 4-slot ring either way) and stays in
+# the plan because a weight holds one form: the bucket's alternative is the bf16 kernel at 42 us.  Not adopted, as
+# for p14: qkv (bf16 10.8 -> 11.0 at one row, 12.4 -> 13.3 at 39), o / down at 39 rows (15.7 -> 17.4), the LM head
+# at 39 rows (199.1 -> 202.1).
+_P13_PLAN = {("gate_up", 1), ("gate_up", 16), ("gate_up", 64), ("lm_head", 1), ("lm_head", 16),
+             ("down", 1), ("down", 16)}
+_P13 = {}  # (data_ptr, N, K) of a registered bf16 weight -> Packed13Weight
+P13_EXCAP = 8  # exceptions per 16-row group (stream_gemm.hip P13_EXCAP)
+P13_DEFAULT = "1"
+
+
+class Packed13Weight:
+    """A bf16 decode weight [N, K] with its p13 tiles: ``packed`` uint8 [N * K * 13 / 8], ``base7``, the exception
+    list (``exoff`` int32 [N / 16 + 1] offsets per 16-row group into ``exlist`` int32 words, ``nex`` of them) and
+    the ``packable`` verdict (no group above P13_EXCAP exceptions; an unpackable weight has no tiles)."""
+
+    def __init__(self, w, packed, base7, exoff, exlist, nex, packable, role):
+        self.w, self.packed, self.base7, self.exoff, self.exlist = w, packed, base7, exoff, exlist
+        self.nex, self.packable, self.role = nex, packable, role
+
+    def nbytes(self) -> int:
+        if self.packed is None:
+            return 0
+        return self.packed.numel() + 4 * (self.exoff.numel() + self.exlist.numel())
+
+
+def p13_enabled() -> bool:
+    return p14_enabled() and os.environ.get("MRSUM_P13", P13_DEFAULT) == "1"
+
+
+def p13_role_used(role: str) -> bool:
+    return any(r == role for r, _ in _P13_PLAN)
+
+
+def p13_takes(role: str, M: int) -> bool:
+    return p13_enabled() and (role, p14_bucket(M)) in _P13_PLAN
+
+
+def p13_pack(w: torch.Tensor):
+    """(tiles uint8 [N * K * 13 / 8], base7, exoff int32 [N / 16 + 1], exlist int32 [max(nex, 1)], nex, largest
+    per-group exception count) of a bf16 [N, K] matrix, packed on the GPU (synchronises: a load-time step).  The
+    list is in (group, word) order; a group above P13_EXCAP contributes its first-arrived P13_EXCAP words (the
+    matrix is unpackable then)."""
+    _bf16_cuda(w)
+    _req(w.dim() == 2 and w.is_contiguous() and w.shape[0] % 16 == 0 and w.shape[1] % 128 == 0
+         and w.shape[1] // 128 < 0x3fff, "p13_pack: expected a contiguous bf16 [16 n, 128 k] matrix")
+    N, K = w.shape
+    G = N // 16
+    packed = torch.empty(N * K // 8 * 13, dtype=torch.uint8, device=w.device)
+    stats = torch.zeros(2, dtype=torch.int32, device=w.device)
+    excnt = torch.zeros(G, dtype=torch.int32, device=w.device)
+    exbuf = torch.full((G, P13_EXCAP), -1, dtype=torch.int32, device=w.device)
+    _check(_fn("mrsum_p13_pack")(_p(w), N, K, _p(packed), _p(stats), _p(excnt), _p(exbuf), _stream()), "p13_pack")
+    mx, nex = (int(v) for v in stats.tolist())
+    exoff = torch.zeros(G + 1, dtype=torch.int32, device=w.device)
+    exlist = torch.zeros(1, dtype=torch.int32, device=w.device)
+    worst = 0
+    if nex:
+        worst = int(excnt.max())
+        kept = excnt.clamp(max=P13_EXCAP)
+        exoff[1:] = torch.cumsum(kept, 0)
+        # unsigned order of the words; the unused slots (all ones) sort last
+        srt = torch.sort(exbuf.to(torch.int64) & 0xffffffff, dim=1).values
+        keep = torch.arange(P13_EXCAP, device=w.device)[None, :] < kept[:, None]
+        words = srt[keep]
+        exlist = torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32).contiguous()
+    return packed, max(mx - 14, 1), exoff, exlist, nex, worst
+
+
+def p13_attach(w: torch.Tensor, role: str) -> Packed13Weight:
+    """Pack ``w`` as p13 and register it; a matrix with a group above the exception cap is left unregistered."""
+    _req(role in P14_ROLES, "p13_attach: unknown role %r" % (role,))
+    packed, base7, exoff, exlist, nex, worst = p13_pack(w)
+    if worst > P13_EXCAP:
+        return Packed13Weight(w, None, base7, None, None, nex, False, role)
+    pw = _P13[(w.data_ptr(), w.shape[0], w.shape[1])] = Packed13Weight(w, packed, base7, exoff, exlist, nex, True, role)
+    return pw
+
+
+def p13_detach(w: torch.Tensor) -> None:
+    _P13.pop((w.data_ptr(), w.shape[0], w.shape[1]), None)
+
+
+def packed_attach(w: torch.Tensor, role: str):
+    """The one packed form of a decode weight: p13 if its role reads it and the matrix is p13-packable, else p14 if
+    its role reads that (an unpackable matrix keeps the bf16 kernel), else None.  Undone by packed_detach."""
+    if p13_enabled() and p13_role_used(role):
+        p3 = p13_attach(w, role)
+        if p3.packable:
+            return p3
+    return p14_attach(w, role) if p14_enabled() and p14_role_used(role) else None
+
+
+def packed_detach(w: torch.Tensor) -> None:
+    p13_detach(w)
+    p14_detach(w)
+
+
+def p13_lookup(w: torch.Tensor) -> Optional[Packed13Weight]:
+    return _P13.get((w.data_ptr(), w.shape[0], w.shape[1]))
 
 
 def linear_takes_norm(M: int, N: int, K: int) -> bool:
@@ -1395,8 +1516,9 @@ def add_rmsnorm_parts(parts: torch.Tensor, residual: torch.Tensor, w: torch.Tens
 # Plan = ("stream", wpb, S) | ("skinny", nt, S) | ("lds", S) | ("gemm",) (the 256 x 256-tile kernel)
 N_CU = 256
 # host-side launch counts of selected paths (tests check which path ran); stream_p14 / stream_bf16: which form
-# of the weight a stream GEMM launch read
-STATS = {"tp_push": 0, "stream_p14": 0, "stream_bf16": 0}
+# of the weight a stream GEMM launch read (stream_p14: the packed kernel in either width, stream_p13: its 13-bit
+# subset)
+STATS = {"tp_push": 0, "stream_p14": 0, "stream_p13": 0, "stream_bf16": 0}
 
 
 def stream_config(N: int, K: int, swiglu: bool = False, splits: Optional[int] = None, max_splits: int = 16):

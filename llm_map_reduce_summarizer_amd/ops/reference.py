@@ -293,6 +293,82 @@ def p14_unpack_ref(packed: torch.Tensor, base7: int, N: int, K: int) -> torch.Te
     return u.to(torch.int16).view(torch.bfloat16)
 
 
+# ------------------------------------------------------------------ p13: 13 bits and an exception list
+# Bit-level reference of stream_gemm.hip "p13": hi as the 5-bit code (sign << 4) | c4, c4 = 0 for e7 = 0, else
+# e7 - base7 + 1 in 1..15, base7 = max(max e7 - 14, 1).  An element with 0 < e7 < base7 is an exception: c4 = 0 in
+# the tile and the word kb << 18 | lane << 12 | (8 i + e) << 7 | e7 in the list, which is sorted by (16-row
+# group, word) with offsets per group.  One 3328-byte tile per (group, k block), lanes as p14:
+# [0, 2048) lo plane, [2048, 3072) c4 nibbles (both as p14), [3072, 3328) one sign dword per lane, the sign of
+# (i, e) at bit 8 (e & 3) + 2 i + (e >> 2).
+P13_TILE = 3328
+P13_WINDOW = 15
+P13_EXCAP = 8  # a matrix is packable iff no 16-row group holds more exceptions
+
+
+def p13_base7(w: torch.Tensor) -> int:
+    return max(int(((p14_bits(w) >> 8) & 0x7f).max()) - (P13_WINDOW - 1), 1)
+
+
+def p13_pack_ref(w: torch.Tensor):
+    """bf16 [N, K] (N % 16 == 0, K % 128 == 0) -> (uint8 [N * K * 13 / 8] tiles, base7, exoff int32 [N / 16 + 1],
+    exlist int32 [exceptions] (the 32-bit words), largest per-group exception count).  The matrix is packable iff
+    that count is at most P13_EXCAP; the list of an unpackable matrix is still complete here."""
+    N, K = w.shape
+    assert w.dtype == torch.bfloat16 and N % 16 == 0 and K % 128 == 0 and K // 128 < 0x3fff
+    u = _p14_lanes(p14_bits(w))  # [T, 64, 4, 8]
+    base7 = p13_base7(w)
+    e7 = (u >> 8) & 0x7f
+    exc = (e7 != 0) & (e7 < base7)
+    c4 = torch.where((e7 == 0) | exc, torch.zeros_like(e7), e7 - base7 + 1)
+    assert int(c4.max()) <= P13_WINDOW
+    sg = u >> 15
+    T = u.shape[0]
+    lo = (u & 0xff).reshape(T, 64, 2, 16).permute(0, 2, 1, 3).reshape(T, 2048)
+    nib = (c4[..., :4] | c4[..., 4:] << 4).reshape(T, 1024)
+    sgn = torch.zeros(T, 64, dtype=torch.int64, device=u.device)
+    for i in range(4):
+        for e in range(8):
+            sgn |= sg[:, :, i, e] << (8 * (e & 3) + 2 * i + (e >> 2))
+    sgn = torch.stack([(sgn >> (8 * k)) & 0xff for k in range(4)], dim=-1).reshape(T, 256)
+    tiles = torch.cat([lo, nib, sgn], dim=1).to(torch.uint8).reshape(-1)
+    nkb = K // 128
+    t, lane, i, e = torch.nonzero(exc, as_tuple=True)
+    word = (t % nkb) << 18 | lane << 12 | (8 * i + e) << 7 | e7[t, lane, i, e]
+    grp = t // nkb
+    order = torch.argsort(grp * 2 ** 32 + word)
+    grp, word = grp[order], word[order]
+    cnt = torch.bincount(grp, minlength=N // 16)
+    exoff = torch.zeros(N // 16 + 1, dtype=torch.int64)
+    exoff[1:] = torch.cumsum(cnt, 0)
+    exlist = torch.where(word >= 2 ** 31, word - 2 ** 32, word).to(torch.int32)
+    return tiles, base7, exoff.to(torch.int32), exlist, int(cnt.max()) if cnt.numel() else 0
+
+
+def p13_unpack_ref(packed: torch.Tensor, base7: int, exoff: torch.Tensor, exlist: torch.Tensor, N: int,
+                   K: int) -> torch.Tensor:
+    """Inverse of p13_pack_ref: the original bf16 [N, K], bit for bit, exceptions restored from the list."""
+    t = packed.reshape(-1, P13_TILE).to(torch.int64)
+    T = t.shape[0]
+    lo = t[:, :2048].reshape(T, 2, 64, 2, 8).permute(0, 2, 1, 3, 4).reshape(T, 64, 4, 8)
+    nb = t[:, 2048:3072].reshape(T, 64, 4, 4)
+    c4 = torch.cat([nb & 15, nb >> 4], dim=-1)
+    sb = t[:, 3072:].reshape(T, 64, 4)
+    sgn = sum(sb[..., k] << (8 * k) for k in range(4))
+    e7 = torch.where(c4 == 0, c4, c4 + base7 - 1)
+    nkb = K // 128
+    words = exlist.to(torch.int64) & 0xffffffff
+    for G in range(N // 16):
+        for x in words[int(exoff[G]):int(exoff[G + 1])].tolist():
+            e7[G * nkb + (x >> 18), (x >> 12) & 63, (x >> 10) & 3, (x >> 7) & 7] = x & 127
+    hi = torch.zeros_like(lo)
+    for i in range(4):
+        for e in range(8):
+            hi[:, :, i, e] = ((sgn >> (8 * (e & 3) + 2 * i + (e >> 2))) & 1) << 7 | e7[:, :, i, e]
+    u = (hi << 8 | lo).reshape(N // 16, K // 128, 4, 16, 4, 8).permute(0, 3, 1, 4, 2, 5).reshape(N, K)
+    u = torch.where(u >= 0x8000, u - 0x10000, u)
+    return u.to(torch.int16).view(torch.bfloat16)
+
+
 def linear(x: torch.Tensor, w) -> torch.Tensor:
     if isinstance(w, Fp8Weight):
         return (x.float() @ w.dequant().t()).to(x.dtype)
